@@ -2,8 +2,13 @@
 """DGC hot-path benchmark on MI355X: compensate -> compress (sample, threshold,
 select, adaptation, masking) -> RCCL allgather -> decompress, all on the device.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full [--no-cpu]]
     torchrun --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+``--dump-outputs DIR`` is given, and prints the result line. ``--full`` adds everything
+that takes runs of its own: the other issue mode and the dense fill, the allgather
+probe, ``selection_steps``, ``hbm_probe``, the drop-in comparison and the CPU baselines.
 
 Workloads (BASELINE.json configs; synthetic data of their shapes):
   flat-1B       (default) 1e9-element fp32 bucket, ratio 0.001, nesterov, fp32/int64  [configs[3]]
@@ -18,6 +23,12 @@ second (each rank compresses its own replica's gradients: weak scaling). ``roofl
 is for the dominant kernel, K1 (compensate + fused sample + candidate lists), timed
 with HIP events on the stream it runs on; ``step_hbm`` is the whole step's algorithmic
 HBM rate. With ``--gpus N`` and no torchrun, N ranks are spawned on 127.0.0.1.
+
+``--dump-outputs DIR`` (rank 0): what the last timed step handed its caller, as
+``DIR/<name>.npy`` — the decompressed gradient ``out`` (a model set: the batch's flat
+output and ``dense_out``) as a fixed, seeded sample of its elements when it is large,
+plus ``out``'s non-zero entries (``out_nonzero_index`` ascending, ``out_nonzero_value``).
+The same arguments give the same inputs, so two builds compare array for array.
 """
 import argparse
 import contextlib
@@ -64,6 +75,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="flat-1B", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what takes runs of its own: the other issue mode and the "
+                         "dense fill, the allgather probe, selection_steps, hbm_probe, the drop-in comparison and the "
+                         "CPU baselines (--no-extras / --no-cpu drop parts of it); off: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes the last timed step's outputs as DIR/<name>.npy (float32 / float64, under "
+                         "64 MB: large arrays as a fixed, seeded sample)")
     ap.add_argument("--cpu-numel", type=float, default=1e9,
                     help="CPU baseline (all cores), flat: elements per step (default: the whole 1B bucket)")
     ap.add_argument("--cpu-numel-1t", type=float, default=5e7, help="CPU-baseline sample (1 thread), flat")
@@ -71,19 +89,23 @@ def parse():
     ap.add_argument("--inputs", default="per-step", choices=["per-step", "alternating"],
                     help="per-step: a fresh gradient per rank and step (SURVEY.md §8d, the headline); alternating: "
                          "two buffers per rank, steps alternating between them (rounds 1-5's input model)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--rccl-one-rank", action="store_true",
                     help="N=1: exchange through a one-rank RCCL group as at N > 1 (the allgather path and its "
                          "timing executed on a one-GPU box); not the headline configuration")
     ap.add_argument("--phases", action="store_true", help="HIP events around every phase (adds markers)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the dense-fill pass and (W = 1) the drop-in DistributedOptimizer comparison")
+                    help="with --full: skip the issue-mode and dense-fill passes and (W = 1) the drop-in "
+                         "DistributedOptimizer comparison")
     ap.add_argument("--dropin-model", default="resnet50", choices=["resnet50", "vgg16_bn"],
                     help="model set of the drop-in comparison of a flat workload's run")
     ap.add_argument("--fill", default="sparse", choices=["inline", "allgather", "sparse"],
                     help="decompress zero_(): sparse = re-zero only the previous step's entries of the bench's "
                          "persistent output (the bench owns it and never writes it; dgc/bucket.py)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---------------------------------------------------------------------------- CPU baseline
@@ -304,6 +326,10 @@ class FlatRun:
     def probe_buffers(self):
         return [self.grads[0], self.grads[1], self.out], [self.b._mmt, self.b._vec]
 
+    def outputs(self):
+        """What a step hands its caller: the decompressed gradient."""
+        return {"out": self.out}
+
     def info(self):
         return self.b.last_info()
 
@@ -420,6 +446,11 @@ class ModelRun:
     def probe_buffers(self):
         b = self.b
         return [self.grads[0][0], self.grads[1][0], b.out_flat], [b._mmt_flat, b._vec_flat]
+
+    def outputs(self):
+        """What a step hands its caller: the compressed tensors' decompressed gradients
+        (the batch's flat output) and the dense tensors' compensated averages."""
+        return {"out": self.b.out_flat, "dense_out": self.dense_out}
 
     def k1_bytes(self):
         # every compressed tensor: read g, mmt, vec; write mmt, vec; plus the samples written
@@ -683,6 +714,63 @@ def step_bytes(run, world, full_passes):
     return contract, required
 
 
+# ---------------------------------------------------------------------------- --dump-outputs
+DUMP_SAMPLE = 1 << 21          # elements kept of a larger array (8 MB as float32, 16 MB as float64)
+DUMP_LIMIT_BYTES = 64 << 20    # all arrays of one dump together
+DUMP_SEED = 0xD6C
+
+
+def sample_positions(n, m=None, seed=DUMP_SEED):
+    """None when an ``n``-element array is written whole (n <= m, by default DUMP_SAMPLE),
+    else the ``m`` ascending positions in [0, n) kept of it: a function of (seed, n, m)
+    only, so every run and every build keeps the same elements."""
+    m = DUMP_SAMPLE if m is None else m
+    if n <= m:
+        return None
+    import numpy as np
+    return np.sort(np.random.default_rng([seed, n, m]).integers(0, n, size=m, dtype=np.int64))
+
+
+def nonzero_entries(t, chunk=1 << 28):
+    """(indices, values) of the flat tensor's non-zero entries, indices ascending (int64),
+    found ``chunk`` elements at a time."""
+    idx = [torch.nonzero(t[c0: c0 + chunk]).view(-1) + c0 for c0 in range(0, t.numel(), chunk)]
+    idx = torch.cat(idx) if idx else torch.zeros(0, dtype=torch.int64, device=t.device)
+    return idx, t[idx]
+
+
+def dump_outputs(run, path):
+    """Writes ``run.outputs()`` — what the last step handed its caller — to ``path`` as
+    <name>.npy (float32), each array whole or as ``sample_positions`` of its flattened
+    elements, and the non-zero entries of ``out`` (the decompressed gradient is zero but
+    for the gathered entries): out_nonzero_index (float64, exact below 2^53; ascending) and
+    out_nonzero_value, sampled alike when there are more than DUMP_SAMPLE. Returns
+    {name: {"numel": elements of the full array, "kept": elements written}}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays, desc = {}, {}
+
+    def keep(name, t, dtype):
+        t = t.reshape(-1)
+        pos = sample_positions(t.numel())
+        kept = t if pos is None else t[torch.from_numpy(pos).to(t.device)]
+        arrays[name] = kept.to(dtype).cpu().numpy()
+        desc[name] = {"numel": t.numel(), "kept": int(arrays[name].size)}
+
+    outs = run.outputs()
+    for name, t in outs.items():
+        keep(name, t, torch.float32)
+    idx, val = nonzero_entries(outs["out"].reshape(-1))
+    keep("out_nonzero_index", idx, torch.float64)
+    keep("out_nonzero_value", val, torch.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the limit of {DUMP_LIMIT_BYTES}")
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return desc
+
+
 @contextlib.contextmanager
 def _stdout_to_stderr():
     """File-descriptor level: RCCL prints its version banner to stdout when a
@@ -779,8 +867,10 @@ def main():
         elapsed = t.item()
     ms = {p: sum(e[p][0].elapsed_time(e[p][1]) for e in evs) / args.steps for p in timed}
     info = run.info()
+    # the last timed step's outputs, before anything below steps on or overwrites the state
+    dumped = dump_outputs(run, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     extras = {}
-    if coll and not args.no_extras and getattr(run.b, "xchg", None) is None:
+    if args.full and coll and not args.no_extras and getattr(run.b, "xchg", None) is None:
         # the step again with the single allgather issued the other way (dgc/comm.py
         # COLLECTIVE_ISSUE): on the current stream vs on torch's collective stream + wait
         from dgc import comm
@@ -796,7 +886,7 @@ def main():
             f"{other}_ms_per_step": round(other_ms, 4),
             "note": "current = all_gather_into_tensor(async_op=False), run by torch on the caller's stream; async = "
                     "async_op=True + wait(), on torch's collective stream joined by events"}
-    if not args.no_extras and run.b.fill == "sparse":
+    if args.full and not args.no_extras and run.b.fill == "sparse":
         # the same steps with the reference's dense zero_() (dgc/compression.py:191) before
         # the scatter: what the persistent output's re-zero saves. The flat bucket goes on
         # from the same state; a model set gets a fresh batch built with fill="inline"
@@ -810,9 +900,11 @@ def main():
         extras["dense_fill"] = {"ms_per_step": round(dense, 4), "steps": args.steps,
                                 "note": "fill inline: the whole output zeroed every step (4 B/elem), as the "
                                         "reference's grad.zero_(); value/ms_per_step above use fill sparse"}
-    xgmi = allgather_probe(run, world) if coll else None
-    sel_steps = selection_steps(run, args.steps, nsteps)
-    probe = hbm_probe(*run.probe_buffers())   # after the timed steps: overwrites the state
+    xgmi = sel_steps = probe = None
+    if args.full:
+        xgmi = allgather_probe(run, world) if coll else None
+        sel_steps = selection_steps(run, args.steps, nsteps)
+        probe = hbm_probe(*run.probe_buffers())   # after the timed steps: overwrites the state
     ms_step = elapsed * 1e3 / args.steps
     full_passes = info.get("full_passes", 0)
     contract, required = step_bytes(run, world, full_passes)
@@ -859,13 +951,18 @@ def main():
                      "achieved_GBs": required / (ms_step * 1e-3) / 1e9,
                      "frac_of_8TBs": required / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
                      "frac_of_measured_copy": required / (ms_step * 1e-3) / 1e9 / HBM_COPY_GBS},
-        "hbm_probe": dict(probe, k1_frac_of_probe=k1_gbs / probe["GBs"],
-                          step_frac_of_probe=required / (ms_step * 1e-3) / 1e9 / probe["GBs"]),
         "phase_ms": {p: round(v, 4) for p, v in ms.items()},
         "compensate_ms_per_step": [round(e["compensate"][0].elapsed_time(e["compensate"][1]), 3) for e in evs],
         "selection": info,
-        "selection_steps": sel_steps,
     }
+    if args.full:
+        res["hbm_probe"] = dict(probe, k1_frac_of_probe=k1_gbs / probe["GBs"],
+                                step_frac_of_probe=required / (ms_step * 1e-3) / 1e9 / probe["GBs"])
+        res["selection_steps"] = sel_steps
+    if dumped is not None:
+        res["outputs"] = {"dir": args.dump_outputs, "arrays": dumped,
+                          "note": "the last timed step's outputs as <name>.npy; kept < numel: the elements at "
+                                  f"sample_positions(numel) (seed {DUMP_SEED:#x})"}
     if coll:
         res["collectives_per_step"] = {name: c / args.steps for name, c in counts.items()}
     if xgmi is not None and world == 1:   # --rccl-one-rank: the collective's own cost, no link traffic
@@ -884,7 +981,7 @@ def main():
                                          "stream around issue + completion); peak = (W-1) x 153 GB/s of xGMI links; "
                                          "ceiling = the same collective of 256 MB per rank in this run"}, **xgmi)
     log(f"{args.workload}: {ms_step:.3f} ms/step on the GPU")
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         model = wl["model"] if wl["kind"] == "model" else args.dropin_model
         try:
             log(f"drop-in DistributedOptimizer comparison on {model}")
@@ -892,7 +989,7 @@ def main():
         except Exception as e:   # an extra must not cost the headline line
             res["dropin"] = {"error": f"{type(e).__name__}: {e}"}
     res.update(extras)
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         cores = cpu_cores()
         log(f"CPU baseline on {cores} threads, then 1 thread")
         res["cpu_baseline"] = cpu_baseline(run, wl, args.cpu_numel, args.cpu_steps, cores)

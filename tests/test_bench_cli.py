@@ -53,6 +53,56 @@ def test_step_gradients_are_seeded_per_rank_and_step():
     assert torch.equal(h, h.to(torch.bfloat16).float())   # bf16-origin values held in fp32
 
 
+def test_plain_run_is_the_default_and_full_is_opt_in(monkeypatch):
+    b = _bench()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = b.parse()
+    assert a.full and a.dump_outputs == "d"
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        b.parse()
+
+
+class _FakeOutputs:
+    def __init__(self, out, dense):
+        self.out, self.dense = out, dense
+
+    def outputs(self):
+        return {"out": self.out, "dense_out": self.dense}
+
+
+def test_dump_outputs_writes_whole_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: small arrays whole, large ones at sample_positions (a function of
+    the size alone), out's non-zero entries in index order; float32 / float64 files."""
+    import numpy as np
+    import torch
+    b = _bench()
+    monkeypatch.setattr(b, "DUMP_SAMPLE", 1000)
+    assert b.sample_positions(1000, 1000) is None
+    pos = b.sample_positions(50_000, 1000)
+    assert pos.shape == (1000,) and np.all(np.diff(pos) >= 0) and 0 <= pos[0] and pos[-1] < 50_000
+    assert np.array_equal(pos, b.sample_positions(50_000, 1000))
+    out = torch.zeros(50_000)
+    nz = torch.arange(7, 50_000, 41)          # 1219 entries: more than the sample
+    out[nz] = torch.arange(1, nz.numel() + 1, dtype=torch.float32)
+    dense = torch.arange(300, dtype=torch.float32).view(3, 100)
+    desc = b.dump_outputs(_FakeOutputs(out, dense), str(tmp_path / "d"))
+    got = {n: np.load(tmp_path / "d" / f"{n}.npy") for n in desc}
+    assert set(got) == {"out", "dense_out", "out_nonzero_index", "out_nonzero_value"}
+    assert got["out"].dtype == np.float32 and np.array_equal(got["out"], out.numpy()[pos])
+    assert np.array_equal(got["dense_out"], dense.numpy().reshape(-1))
+    keep = b.sample_positions(nz.numel(), 1000)
+    assert got["out_nonzero_index"].dtype == np.float64
+    assert np.array_equal(got["out_nonzero_index"], nz.numpy()[keep].astype(np.float64))
+    assert np.array_equal(got["out_nonzero_value"], out.numpy()[nz.numpy()[keep]])
+    assert desc["out"] == {"numel": 50_000, "kept": 1000} and desc["dense_out"] == {"numel": 300, "kept": 300}
+    idx, val = b.nonzero_entries(out, chunk=999)   # chunked search: same entries
+    assert torch.equal(idx, nz) and torch.equal(val, out[nz])
+
+
 class _FakeFlat:
     def __init__(self, b, n, steps):
         import torch

@@ -30,8 +30,8 @@ def main():
             e = dict(os.environ)
             e.update(env)
             out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5",
-                                  "--workload", wl, "--no-cpu", "--no-extras"], env=e, capture_output=True, text=True,
-                                 timeout=600)
+                                  "--workload", wl, "--full", "--no-cpu", "--no-extras"], env=e, capture_output=True,
+                                 text=True, timeout=600)
             if out.returncode != 0:
                 print(out.stderr[-3000:], file=sys.stderr)
                 raise SystemExit(f"{label}: bench failed ({out.returncode})")

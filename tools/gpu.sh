@@ -2,7 +2,7 @@
 # Every GPU-box procedure of this repo in one script (run it through gpurun):
 #
 #   tools/gpu.sh tests OUT [pytest args...]    the -m gpu suite (or the files / -k given), -v log in OUT/tests.log
-#   tools/gpu.sh bench OUT WL...               bench.py lines (20 steps, 5 warmup, no CPU baseline) + a table
+#   tools/gpu.sh bench OUT WL...               bench.py --full lines (20 steps, 5 warmup, no CPU baseline) + a table
 #   tools/gpu.sh profile OUT WL...             per workload: the bench line, a rocprofv3 --kernel-trace --stats
 #                                              run of the same command, one --pmc pass each for FETCH_SIZE and
 #                                              WRITE_SIZE (summarise with tools/profile_summary.py)
@@ -34,14 +34,14 @@ tests)
   exit $rc ;;
 bench)
   for wl in "${@:-flat-1B}"; do
-    timeout -k 10 600 python bench.py --steps 20 --warmup 5 --workload "$wl" --no-cpu ${BENCH_ARGS:-} \
+    timeout -k 10 600 python bench.py --steps 20 --warmup 5 --workload "$wl" --full --no-cpu ${BENCH_ARGS:-} \
         > "$OUT/bench_$wl.json" 2> "$OUT/bench_$wl.err" || { tail -20 "$OUT/bench_$wl.err"; exit 1; }
   done
   python tools/bench_table.py "$OUT"/bench_*.json ;;
 profile)
   # SUFFIX names a variant's files (e.g. _alternating with BENCH_ARGS="--inputs alternating")
   for wl in "$@"; do
-    CMD="bench.py --gpus 1 --steps 20 --warmup 5 --workload $wl --no-extras ${BENCH_ARGS:-}"
+    CMD="bench.py --gpus 1 --steps 20 --warmup 5 --workload $wl --full --no-extras ${BENCH_ARGS:-}"
     W="$wl${SUFFIX:-}"
     timeout -k 10 600 python $CMD > "$OUT/bench_$W.json" 2> "$OUT/bench_$W.err" || exit 1
     timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$OUT/prof_$W" -o run \
@@ -55,7 +55,7 @@ profile)
 timeline)
   for wl in "$@"; do
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$OUT/prof_$wl" -o run --output-format csv \
-        -- python bench.py --steps 10 --warmup 3 --workload "$wl" --no-cpu --no-extras > "$OUT/bench_$wl.json" \
+        -- python bench.py --steps 10 --warmup 3 --workload "$wl" --full --no-cpu --no-extras > "$OUT/bench_$wl.json" \
         2> "$OUT/prof_$wl.err" || exit 1
     python tools/profile_summary.py "$wl" "$OUT/prof_$wl" none "$OUT/sum" "$OUT/bench_$wl.json" > /dev/null || exit 1
     cat "$OUT/sum/step_timeline_$wl.txt"
