@@ -28,7 +28,7 @@
 //
 // Phases, by the size of the range still being partitioned:
 //   > kNthGMinCand      (select.hip) in global memory by G co-resident workgroups per
-//                       tensor, a barrier among them per pass (k_nth_global);
+//                       tensor, a barrier among them per pass (k_nth_select's grid T x G);
 //   > kNthLds entries   in global memory (L2 / Infinity-Cache resident), 8 waves, each
 //                       over a contiguous stretch, 8 tiles of loads in flight per lane;
 //   > kNthWave entries  in LDS, same 8-wave step (four barriers per step);
@@ -955,7 +955,7 @@ __device__ __forceinline__ void nth_tail_wave(DGC_LDS uint64_t* q, DGC_LDS uint6
 
 // ---------------------------------------------------------------- multi-workgroup global phase
 // The global-memory steps (range > kNthLds) spread over G workgroups of one tensor
-// (k_nth_global, a plain launch sized so that all of them fit at once): one
+// (k_nth_select's G workgroups per tensor, a plain launch sized so that all fit at once): one
 // workgroup's loads in flight bound the one-workgroup phase (57k candidates: 50 us in
 // 2 steps, tools/k5_prof.py). The step is the same partition as nth_step_wg — the G x
 // 8 waves take contiguous stretches in order, so every stopper's rank is the same —
@@ -1087,7 +1087,7 @@ __device__ void nthg_prepare(uint64_t* q, NthG* g, int64_t nth) {
 // G); on return g->f / l / depth / heap_exit hold where the one-workgroup kernel goes on.
 // Ranges of <= min_run entries are left to the one-workgroup phase: below ~140k
 // candidates the four cross-XCD barriers per step cost more than the spread saves
-// (tools/k5ab.sh: 100k 0.28 vs 0.25 ms, 500k 0.43 vs 0.94, 1M 0.55 vs 1.44).
+// (100k 0.28 vs 0.25 ms, 500k 0.43 vs 0.94, 1M 0.55 vs 1.44; DESIGN.md §5, the K5 item).
 // mk: kNthGMk bytes of the caller's LDS (k_nth_select lends the replay's area).
 __device__ __forceinline__ void nth_global_multi(uint64_t* q, int64_t n, int64_t nth, uint32_t* lpos, uint32_t* rpos, NthG* g,
                                  uint32_t b, uint32_t G, int64_t min_run, uint32_t G_expected, DGC_LDS uint8_t* mk) {
@@ -1262,7 +1262,8 @@ __device__ __forceinline__ void nth_global_multi(uint64_t* q, int64_t n, int64_t
 // lq: the caller's LDS area of kNthLds entries (16-B aligned): the partition range
 // in the LDS phase, the stopper bytes in the global phase; llp / lrp (kNthPairLds
 // each) and lmk (kNthMkLds bytes): the LDS phase's pair slots and stopper bytes.
-// from: the state k_nth_global left (its global phase done), or null (start at [0, n)).
+// from: the state nth_global_multi left (the global phase done by the tensor's G
+// workgroups), or null (start at [0, n)).
 __device__ __forceinline__ void nth_element_wg(DGC_GLB uint64_t* q, int64_t n, int64_t nth, DGC_GLB uint32_t* gpos_l,
                                                DGC_GLB uint32_t* gpos_r, DGC_LDS uint64_t* lq, DGC_LDS uint32_t* llp,
                                                DGC_LDS uint32_t* lrp, DGC_LDS uint8_t* lmk,

@@ -92,11 +92,10 @@ constexpr float kSpecMarginMax = 0.985f;
 constexpr float kSpecCeilUp = 0.005f, kSpecCeilDown = 0.05f;
 // K5s, the set path of an untied resample (resample_order = 1; see k_resample_set): one
 // launch, workgroups per tensor by its candidate capacity (BT_SET) — one up to
-// kSetCoopMin, kSetG up to kSetG x kSetCoopMin, up to kSetGBig beyond (VGG-16-BN's fc6) —
-// kSetRegC rounds of 1024 keys per workgroup in registers (32 spilled the radix
-// passes' registers to scratch), up to kSetRoundsMax rounds from L2 beyond.
-constexpr int kSetG = 16;                       // the most workgroups of a set's minimum (DGC_SET_G)
-constexpr int kSetGDefault = 4;                 // ... and the default: a cooperative set's fewest workgroups
+// kSetCoopMin, then one per kSetCoopMin candidates, from kSetGDefault to kSetGBig
+// (VGG-16-BN's fc6) — kSetRegC rounds of 1024 keys per workgroup in registers (32 spilled
+// the radix passes' registers to scratch), up to kSetRoundsMax rounds from L2 beyond.
+constexpr int kSetGDefault = 4;                 // a cooperative set's fewest workgroups
 constexpr int kSetGBig = 128;
 constexpr int kSetRegC = 16;
 constexpr int kSetRoundsMax = 64;
@@ -109,7 +108,7 @@ constexpr int kSpecWords = 8;                   // per-tensor speculation state 
 constexpr int kChainOneWords = 256;             // SelWS::chain: k_chain_one's words (zeroed every call) ...
 constexpr int kChainWords = kChainOneWords + 128;   // ... then k_rs_passes' (zero at rest)
 constexpr int kEmitSplit = 4;                   // k_emit workgroups per group
-constexpr int64_t kSetOneMax = kSetCoopMin;     // K5s: one workgroup up to this many candidates (DGC_SET_ONE)
+constexpr int64_t kSetOneMax = kSetCoopMin;     // K5s: one workgroup up to this many candidates
 constexpr int64_t kQueueFold = 16384;           // k_nth_select emits its replay itself when every k <= this
 
 int64_t payload_layout(int64_t capacity, int vd, int id, int64_t* voff, int64_t* ioff);   // decompress.hip
@@ -217,7 +216,7 @@ struct SelWS {
     uint32_t* cand_key;        // K5: their |x| keys, dense (the set paths read 4 B per candidate, not 8)
     uint32_t* gpos;            // K5: pair slots of the global-memory partition passes
     NthG* nthg;                // [T] K5: the multi-workgroup global phase's state
-    SetG* setg;                // [T] K5s over kSetG workgroups of one launch
+    SetG* setg;                // [T] K5s over a set's workgroups of one launch
     uint32_t* fin_ticket;      // k_nth_select's last-workgroup ticket (zeroed by sel_init_tensor)
     uint32_t* chain;           // k_chain_one's claim / completion / gate words (zeroed by sel_init_tensor)
     int64_t nseg, ngrp;
@@ -256,18 +255,11 @@ struct Layout {
 // lists serve in the steady state. A model set's passes run most steps (its synthetic
 // thresholds jump), and there a 2048-block cap left the big tensors' passes
 // short of HBM rate: 8192 blocks took VGG-16-BN 0.896 -> 0.811 ms, ResNet-50 0.367 ->
-// 0.361 ms, 16384 VGG-16-BN 0.816 -> 0.805 ms, ResNet-50 unchanged (same box, tools/ab_lib.sh).
+// 0.361 ms, 16384 VGG-16-BN 0.816 -> 0.805 ms, ResNet-50 unchanged (same box).
 // K5s: the fewest workgroups of a cooperative set (beyond kSetCoopMin candidates) — the
 // grid holds max(this, ceil(capacity / kSetCoopMin)) per tensor. 16 per tensor made a
 // ResNet-50 step dispatch ~430 workgroups of 1024 threads, and its biggest sets started
-// 12-14 us into the launch (tools/k5s_prof.py); DGC_SET_G overrides (2..16).
-static uint32_t set_gmin() {
-    static const uint32_t g = [] {
-        const char* e = std::getenv("DGC_SET_G");
-        return (uint32_t)(e ? std::min(std::max(std::atoi(e), 2), kSetG) : kSetGDefault);
-    }();
-    return g;
-}
+// 12-14 us into the launch (tools/k5s_prof.py): kSetGDefault.
 
 static inline int64_t bt_blocks(int which, const TDesc& d, int64_t total_seg, int64_t cap_blocks) {
     const int64_t cap = std::max<int64_t>(1, ceil_div(cap_blocks * d.nseg, std::max<int64_t>(1, total_seg)));
@@ -285,7 +277,7 @@ static inline int64_t bt_blocks(int which, const TDesc& d, int64_t total_seg, in
         case BT_SET:   // K5s: a resample set holds count(t_cur) <= cand_cap > k candidates
             if (d.k < 1 || d.cand_cap <= d.k) return 0;
             if (d.cand_cap <= kSetCoopMin) return 1;
-            return std::min<int64_t>(kSetGBig, std::max<int64_t>(set_gmin(), ceil_div(d.cand_cap, kSetCoopMin)));
+            return std::min<int64_t>(kSetGBig, std::max<int64_t>(kSetGDefault, ceil_div(d.cand_cap, kSetCoopMin)));
         case BT_SAMP: {
             const int64_t cnt = d.samp_off < 0 ? d.n : d.S + 1;
             if (cnt <= kSmallN) return 0;   // one-workgroup threshold (k_rs_small_multi)
@@ -785,7 +777,7 @@ __global__ void k_no_lists(SelWS w) {
 // ------------------------------------------------------------------ state
 // Reset tensor t's selection state for this call, by the whole calling workgroup (any
 // size): the workgroup that just produced its sampled threshold (k_rs_small_multi, or
-// the last workgroup of the final k_rs_hist pass — no launch of its own), or
+// the last workgroup of k_rs_passes' final pass — no launch of its own), or
 // k_sel_init for a pure selection (dgc_select, the threshold given).
 __device__ void sel_init_tensor(const SelWS& w, int t, int keep_lists) {
     const TDesc d = w.td[t];   // by value: stores below cannot alias it
@@ -1069,7 +1061,7 @@ __global__ void __launch_bounds__(kBlock) k_rs_reset_samples(SelWS w, int64_t ks
 // the ks-th largest of its window (SampleKeys); for VGG-16-BN's big tensors ~3 ks keys,
 // where the passes were four launches. A window that does not qualify is left to them.
 __global__ void __launch_bounds__(kScanThreads) k_rs_small_multi(SelWS w, const float* vec_flat, int64_t ks1,
-                                                                 int32_t nsmall, int32_t use_hist) {
+                                                                 int32_t nsmall) {
     const int t = w.small[blockIdx.x];
     const TDesc d = w.td[t];   // by value: stores below cannot alias it
     const uint64_t ks = (uint64_t)ks_of(d, t, ks1);
@@ -1080,10 +1072,7 @@ __global__ void __launch_bounds__(kScanThreads) k_rs_small_multi(SelWS w, const 
         uint32_t* gh = reinterpret_cast<uint32_t*>(w.samples + d.whist_off);
         bool take = false;
         if (complete) {   // K1's histogram of the window first (it re-zeroes it), then its keys
-            if (use_hist)
-                take = rs_window_hist_wg(w.samples + d.win_off, cnt, gh, st->win_key, (uint32_t)ks, w.thr + t);
-            else
-                for (int q = threadIdx.x; q < kWinBins; q += kScanThreads) gh[q] = 0;
+            take = rs_window_hist_wg(w.samples + d.win_off, cnt, gh, st->win_key, (uint32_t)ks, w.thr + t);
             if (!take && cnt <= (uint32_t)kWinMax) {
                 rs_window_wg(w.samples + d.win_off, cnt, ks, w.thr + t);
                 take = true;
@@ -1846,8 +1835,7 @@ k_chain_one(const float* __restrict__ vec_flat, SelWS w, SelCfg p) {
 
 
 __device__ __forceinline__ void resample_set_block(const float* __restrict__ vec_flat, const SelWS& w,
-                                                   const EmitOut& o, int bx, int64_t one_max, uint32_t gmin,
-                                                   bool wait);   // K5s, below
+                                                   const EmitOut& o, int bx, bool wait);   // K5s, below
 
 // The few groups of a model gradient set: kEmitSplit workgroups of kGroupSegs threads
 // per group, each scanning the whole group (thread per segment) and emitting its
@@ -1961,12 +1949,11 @@ __device__ __forceinline__ bool emit_wide_part(const float* __restrict__ vec_fla
 
 template <bool SET>
 __global__ void __launch_bounds__(kGroupSegs)
-k_emit_wide_t(const float* __restrict__ vec_flat, SelWS w, EmitOut oa, EmitOut os, int64_t one_max, uint32_t gmin,
-              int32_t ngb) {
+k_emit_wide_t(const float* __restrict__ vec_flat, SelWS w, EmitOut oa, EmitOut os, int32_t ngb) {
     const int bx = (int)blockIdx.x;
     ES_STAMP(0);
     if (SET && bx >= ngb) {
-        resample_set_block(vec_flat, w, os, bx - ngb, one_max, gmin, true);
+        resample_set_block(vec_flat, w, os, bx - ngb, true);
     } else if (emit_wide_part(vec_flat, w, oa, bx) && SET) {   // uniform per workgroup
         const int t = task(w, BT_GRP, bx);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2249,7 +2236,6 @@ struct FinishArgs {
     // ascending order (no tensor took the exact replay's topk order), else 0 — the
     // packed payload's header word 1, read by the W = 1 scatter (whole-granule stores)
     int64_t* order_out;
-    float margin_max;   // the adaptive list margin's ceiling (kSpecMarginMax; DGC_SPEC_MARGIN_MAX for A/B runs)
 };
 
 __device__ __forceinline__ void sel_finish_body(const SelWS& w, const FinishArgs& f) {
@@ -2349,7 +2335,7 @@ __device__ __forceinline__ void sel_finish_body(const SelWS& w, const FinishArgs
             const bool tried = used < __builtin_huge_valf() && tc > 0.f;
             const bool hit = tried && tc >= used;
             const float mcap = !tried ? c0
-                                : hit ? fminf(c0 + kSpecCeilUp, fmaxf(margin, f.margin_max))
+                                : hit ? fminf(c0 + kSpecCeilUp, fmaxf(margin, kSpecMarginMax))
                                       : fmaxf(c0 - kSpecCeilDown, margin);
             float m = margin;
             if (hit) m = fminf(fmaxf(1.05f * (used / tc), margin), mcap);
@@ -2756,8 +2742,8 @@ static_assert(kK5SmemBytes <= 160 * 1024 - 1024, "K5 / K5b LDS");
 // 11-bit passes over the open range up to 0x7FFFFFFF; the emit carries the wire casts
 // and the masking of the K5 emit.
 //
-// Over G co-resident workgroups of ONE launch (the tensor's BT_SET workgroups: kSetG,
-// up to kSetGBig for a capacity past kSetG x kSetCoopMin — VGG-16-BN's fc6, where four
+// Over G co-resident workgroups of ONE launch (the tensor's BT_SET workgroups: kSetGDefault,
+// up to kSetGBig for a capacity past kSetGDefault x kSetCoopMin — VGG-16-BN's fc6, where four
 // sliced launches k_bigset_* ran as no-ops every step before; one for a capacity up to
 // kSetCoopMin, and none for a tensor that cannot resample — a fixed 16 per tensor took
 // ~10 us to dispatch): a set of more than kSetCoopMin candidates is cut into G contiguous
@@ -3031,8 +3017,7 @@ __device__ __forceinline__ void resample_set_body(const float* __restrict__ vec_
 // first wait until all of the tensor's emit workgroups have counted themselves (bounded:
 // past kSetArriveTicks the tensor is left to the exact replay, recorded as a fallback).
 __device__ __forceinline__ void resample_set_block(const float* __restrict__ vec_flat, const SelWS& w,
-                                                   const EmitOut& o, int bx, int64_t one_max, uint32_t gmin,
-                                                   bool wait) {
+                                                   const EmitOut& o, int bx, bool wait) {
     const int t = task(w, BT_SET, bx);
     const uint32_t b = (uint32_t)bx - (uint32_t)w.bt[BT_SET][t];
     SelState* st = w.st + t;
@@ -3041,12 +3026,13 @@ __device__ __forceinline__ void resample_set_block(const float* __restrict__ vec
     const uint32_t Gt = (uint32_t)(w.bt[BT_SET][t + 1] - w.bt[BT_SET][t]);   // this tensor's workgroups
     const int64_t n64 = st->n_cur;
     if (d.k < 1 || n64 <= d.k) return;
-    // this set's workgroups: one up to kSetCoopMin candidates, else kSetG, and for a big
+    // this set's workgroups: one up to kSetCoopMin candidates, else kSetGDefault, and for a big
     // tensor as many as keep its stretches in registers (up to Gt); each stretch's rounds
     // past the registers are read from L2 on every walk, up to kSetRoundsMax per stretch
     const int rounds = (int)((n64 + kScanThreads - 1) / kScanThreads);
     uint32_t G = 1;
-    if (n64 > one_max && Gt > 1) {   // (then Gt >= gmin: n64 <= cand_cap)
+    constexpr uint32_t gmin = kSetGDefault;
+    if (n64 > kSetOneMax && Gt > 1) {   // (then Gt >= gmin: n64 <= cand_cap)
         const uint32_t want = (uint32_t)((rounds + kSetRegC - 1) / kSetRegC);
         G = want > gmin ? (want < Gt ? want : Gt) : gmin;
         G = G < Gt ? G : Gt;
@@ -3082,33 +3068,15 @@ __device__ __forceinline__ void resample_set_block(const float* __restrict__ vec
 }
 
 __global__ void __launch_bounds__(kScanThreads)
-k_resample_set(const float* __restrict__ vec_flat, SelWS w, EmitOut o, int64_t one_max, uint32_t gmin) {
-    resample_set_block(vec_flat, w, o, (int)blockIdx.x, one_max, gmin, false);
+k_resample_set(const float* __restrict__ vec_flat, SelWS w, EmitOut o) {
+    resample_set_block(vec_flat, w, o, (int)blockIdx.x, false);
 }
 
-// K5's global-memory phase by G workgroups per tensor (grid G x T, a plain launch sized
-// so all of them fit at once; a residency consensus decides whether they run it, see
-// introselect.hpp); k_nth_select goes on from the state it leaves. The A/B form
-// (DGC_NTH_SEPARATE=1): by default k_nth_select runs the phase on its own extra
-// workgroups (grid T x G), one launch fewer.
-__global__ void __launch_bounds__(kNthThreads) k_nth_global(SelWS w, uint32_t G, int64_t min_run,
-                                                            uint32_t G_expected) {
-    __shared__ uint8_t mk[kNthGMk];
-    const int t = blockIdx.y;
-    const SelState* st = w.st + t;
-    if (st->branch != DGC_BRANCH_RESAMPLE || st->rs_nth != 1) return;
-    const TDesc d = w.td[t];
-    uint32_t* gl = w.gpos + d.gpos_off;
-    uint32_t* gr = gl + d.cand_cap / 2 + 1;
-    nth_global_multi(w.queue + d.cand_off, st->n_cur, d.k - 1, gl, gr, w.nthg + t, blockIdx.x, G, min_run,
-                     G_expected, lds(mk));
-}
-
-// Grid T x G: workgroup (t, 0) replays tensor t; with G > 1 and `global_here` the
-// tensor's G workgroups (t, 0..G-1) first run K5's global phase (nth_global_multi, its
-// stopper bytes in the replay's LDS area, which is free until the phase ends), and
-// workgroups (t, b > 0) leave after it. from_global: G > 1, the phase ran (here or in
-// k_nth_global) and the replay goes on from the state it left.
+// Grid T x G: workgroup (t, 0) replays tensor t. global_here (G > 1): the tensor's G
+// workgroups (t, 0..G-1) first run K5's global phase (nth_global_multi, its stopper
+// bytes in the replay's LDS area, which is free until the phase ends); the replay goes
+// on from the state the phase left, and workgroups (t, b > 0) leave after it, or stay
+// to emit the queue (queue_here, below).
 // The last of the T workgroups (t, 0) to finish (f.on) then runs the finish of the whole
 // call (T arrivals on one ticket; nothing it writes is read by k_emit_queue).
 //
@@ -3126,10 +3094,10 @@ __global__ void __launch_bounds__(kNthThreads) k_nth_global(SelWS w, uint32_t G,
 // launched. The wait is bounded (~seconds; workgroup (t, 0) never waits on them): past
 // it the payload is incomplete and the call reports DGC_K5_BROKEN through the sink.
 __global__ void __launch_bounds__(kNthThreads) k_nth_select(const float* __restrict__ vec_flat, SelWS w,
-                                                            EmitOut o, int from_global, FinishArgs f,
-                                                            int force_broken, int emit_here, int global_here,
-                                                            uint32_t G, int64_t min_run, uint32_t G_expected,
-                                                            int queue_here, int rebuild_queue) {
+                                                            EmitOut o, FinishArgs f, int force_broken,
+                                                            int emit_here, int global_here, uint32_t G,
+                                                            int64_t min_run, uint32_t G_expected, int queue_here,
+                                                            int rebuild_queue) {
     const int t = blockIdx.x;
     const uint32_t b = blockIdx.y;
     const SelState* st = w.st + t;
@@ -3198,12 +3166,12 @@ __global__ void __launch_bounds__(kNthThreads) k_nth_select(const float* __restr
         __shared__ int recover;
         if (threadIdx.x == 0)
             recover = force_broken ||
-                      (from_global && (__hip_atomic_load(&g->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) &
+                      (global_here && (__hip_atomic_load(&g->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) &
                                        (uint32_t)DGC_K5_BROKEN));
         __syncthreads();
         if (recover) {
-            // a GO phase's workgroups may still be on their way out of a timed-out barrier
-            // (here, not k_nth_global): none touches the queue once it has counted itself
+            // a GO phase's workgroups may still be on their way out of a timed-out barrier:
+            // none touches the queue once it has counted itself
             if (global_here && threadIdx.x == 0 &&
                 __hip_atomic_load(&g->decide, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == kNthGGo)
                 while (__hip_atomic_load(&g->exited, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < G)
@@ -3222,7 +3190,7 @@ __global__ void __launch_bounds__(kNthThreads) k_nth_select(const float* __restr
             for (int64_t j = threadIdx.x; j < nc; j += kNthThreads) q[j] = ((uint64_t)ck[j] << 32) | (uint64_t)j;
             __syncthreads();
         }
-        nth_element_wg(q, nc, d.k - 1, gl, gr, lq, llp, lrp, lmk, from_global && !recover ? g : nullptr);
+        nth_element_wg(q, nc, d.k - 1, gl, gr, lq, llp, lrp, lmk, global_here && !recover ? g : nullptr);
         if (queue_here) {   // the replayed order is in the queue: the extra workgroups emit it
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
@@ -3304,39 +3272,59 @@ static SelCfg cfg_of(const dgc_select_params& p) {
                   p.vdtype, p.idtype,     p.update_memory, p.thr_dtype, p.resample_order == 1 ? 1 : 0};
 }
 
-// The selection of every tensor (its K1 lists kept or not), from k_sel_init to the
-// payload: stream-ordered, and in DGC_SYNC_DEVICE mode with no host synchronisation.
-// k_emit for many groups (flat buckets), k_emit_wide for few (model gradient sets).
-// DGC_EMIT_SHAPE=quarter|wide forces one (the parity tests run both at small sizes).
-static bool emit_is_wide(const Layout& L) {
-    const char* force = std::getenv("DGC_EMIT_SHAPE");
-    return force ? std::strcmp(force, "wide") == 0 : L.ngrp < 256;
+// The library's only environment switches, all three for the parity
+// tests, which reach at small sizes the paths that only large tensors take. Read on every
+// call: the tests set them in-process.
+struct TestHooks {
+    int emit_shape;      // DGC_EMIT_SHAPE=quarter|wide: 0 unset, 1 wide, -1 anything else (k_emit)
+    bool k5_wg;          // DGC_K5_GLOBAL=wg: K5's global phase on one workgroup
+    bool k5_multi;       // DGC_K5_GLOBAL=multi|abort: on several, whatever the candidate counts
+    bool k5_abort;       // DGC_K5_GLOBAL=abort: ... one workgroup short, so the consensus times out
+    int force_broken;    // DGC_K5_FORCE_BROKEN: every replayed tensor recovers a broken global phase
+};
+
+static TestHooks test_hooks() {
+    const char* shape = std::getenv("DGC_EMIT_SHAPE");
+    const char* k5 = std::getenv("DGC_K5_GLOBAL");
+    TestHooks h{};
+    h.emit_shape = !shape ? 0 : std::strcmp(shape, "wide") == 0 ? 1 : -1;
+    h.k5_wg = k5 && std::strcmp(k5, "wg") == 0;
+    h.k5_abort = k5 && std::strcmp(k5, "abort") == 0;
+    h.k5_multi = h.k5_abort || (k5 && std::strcmp(k5, "multi") == 0);
+    h.force_broken = std::getenv("DGC_K5_FORCE_BROKEN") ? 1 : 0;
+    return h;
 }
 
-static int launch_emit(const Layout& L, const float* vec, const SelWS& w, const EmitOut& o, hipStream_t s) {
-    if (emit_is_wide(L))
+// k_emit for many groups (flat buckets), k_emit_wide for few (model gradient sets).
+static bool emit_is_wide(const Layout& L, const TestHooks& hooks) {
+    return hooks.emit_shape ? hooks.emit_shape > 0 : L.ngrp < 256;
+}
+
+static int launch_emit(const Layout& L, const float* vec, const SelWS& w, const EmitOut& o, const TestHooks& hooks,
+                       hipStream_t s) {
+    if (emit_is_wide(L, hooks))
         hipLaunchKernelGGL(k_emit_wide_t<false>, dim3((unsigned)L.grid[BT_GRP]), dim3(kGroupSegs), 0, s, vec, w, o, o,
-                           (int64_t)0, 0u, (int32_t)L.grid[BT_GRP]);
+                           (int32_t)L.grid[BT_GRP]);
     else
         hipLaunchKernelGGL(k_emit, dim3((unsigned)L.grid[BT_GRP]), dim3(kEmitSegs), 0, s, vec, w, o);
     DGC_LAUNCHED();
     return DGC_OK;
 }
 
-// Workgroups per tensor for K5's global phase (k_nth_select's extra workgroups, or
-// k_nth_global's): half the CUs shared among the T tensors, at most kNthGMax. They wait
-// for each other, so all of them must be resident at once: <= CUs / 2 workgroups of 8
-// waves (one fits a CU, with k_nth_select's ~150 KB of LDS as with k_nth_global's 33 KB)
-// guarantee that with this stream's earlier kernels done. (hipLaunchCooperativeKernel checks the same
-// but cost ~29 us per launch on MI355X: more than the phase saves below ~200k candidates.)
-// <= 1 runs the one-workgroup global phase inside k_nth_select instead; so does a call
-// whose tensors all have candidate capacities <= kNthGMinCand, and so does a tensor
-// with <= kNthGMinCand candidates (decided on the device: below ~100k the three
-// cross-XCD barriers per step cost as much as the spread saves, tools/run_k5.sh), and
-// DGC_K5_GLOBAL=wg (A/B, parity); DGC_K5_GLOBAL=multi skips both gates.
+// Workgroups per tensor for K5's global phase (k_nth_select's extra workgroups): half
+// the CUs shared among the T tensors, at most kNthGMax. They wait for each other, so all
+// of them must be resident at once: <= CUs / 2 workgroups of 8 waves (one fits a CU with
+// k_nth_select's ~150 KB of LDS) guarantee that with this stream's earlier kernels done.
+// (hipLaunchCooperativeKernel checks the same but cost ~29 us per launch on MI355X: more
+// than the phase saves below ~200k candidates.)
+// <= 1 keeps the whole replay on one workgroup per tensor; so does a call whose tensors
+// all have candidate capacities <= kNthGMinCand, and so does a tensor with <=
+// kNthGMinCand candidates (decided on the device: below ~100k the three cross-XCD
+// barriers per step cost as much as the spread saves), and the
+// parity tests' DGC_K5_GLOBAL=wg; their DGC_K5_GLOBAL=multi skips both gates.
 constexpr int64_t kNthGMinCand = 98304;    // launch for capacities above, run for candidate counts above
 
-static uint32_t nth_global_groups(int32_t T, int64_t max_cand) {
+static uint32_t nth_global_groups(int32_t T, int64_t max_cand, const TestHooks& hooks) {
     static int per_dev = -1;
     if (per_dev < 0) {
         int dev = 0, cus = 0, per_cu = 0;
@@ -3349,11 +3337,10 @@ static uint32_t nth_global_groups(int32_t T, int64_t max_cand) {
             per_dev = per_cu >= 1 ? cus / 2 : 0;
 
     }
-    const char* force = std::getenv("DGC_K5_GLOBAL");   // wg | multi (parity tests run both)
-    if (force && std::strcmp(force, "wg") == 0) return 0;
-    const bool multi = force && (std::strcmp(force, "multi") == 0 || std::strcmp(force, "abort") == 0);
+    if (hooks.k5_wg) return 0;
+    const bool multi = hooks.k5_multi;
     if (max_cand <= kNthLds || (max_cand <= kNthGMinCand && !multi)) return 0;
-    // measured (tools/run_k5.sh): 16 workgroups per tensor for every tensor of a batch
+    // measured: 16 workgroups per tensor for every tensor of a batch
     // from 40k candidates made ResNet-50 0.358 -> 0.373 ms (864 workgroups launched per
     // step, and at 45-57k candidates the spread phase is no faster than one workgroup:
     // 0.141-0.144 ms either way); it pays from ~100k (500k: 0.945 -> 0.371 ms)
@@ -3364,6 +3351,139 @@ static uint32_t nth_global_groups(int32_t T, int64_t max_cand) {
     return (uint32_t)std::min<int64_t>(g, kNthGMax);
 }
 
+// ---- the count passes of one selection call. A pass runs at t_cur: the list count where
+// t_cur >= t_list, else the full select pass (both gated per tensor on the device); each
+// count kernel's last workgroup per tensor takes the adaptation step. A kernel with an
+// ALIGNED form is launched as `c.al ? k<true> : k<false>`.
+struct SelCall {
+    const float* vec;
+    bool al;   // vec is 16-byte aligned (float4 loads)
+    const SelWS& w;
+    const SelCfg& p;
+    const Layout& L;
+    hipStream_t s;
+};
+
+// the list count and the full pass in one launch, the count also writing the first-k payload
+static int launch_count_emit_pass(const SelCall& c, const EmitOut& o, bool likely_lists) {
+    const int which = likely_lists ? BT_CAP16 : BT_FULL;
+    const unsigned grid = (unsigned)(c.L.grid[BT_CNT] + c.L.grid[which]);
+    hipLaunchKernelGGL(c.al ? k_count_emit_pass<true> : k_count_emit_pass<false>, dim3(grid), dim3(kBlock), 0, c.s,
+                       c.vec, c.w, c.p, o, which, (int)c.L.grid[BT_CNT]);
+    DGC_LAUNCHED();
+    return DGC_OK;
+}
+
+// the list count and the full pass in one launch. A batch's full pass takes two segments
+// per wave, a single tensor's kSuper. Measured (tools/pass_prof.py, ResNet-50): four per
+// wave keep a working workgroup ~9 us on its list appends after 3 us of loads, one per
+// wave ~3 us but 6289 workgroups enter over 10.7 us (the working ones hold the slots);
+// two: 6 us each, all entered within 3.9 us, the pass ends at 15 instead of 18 us —
+// ResNet-50 0.2269 -> 0.2235 ms, VGG-16-BN 0.6275 -> 0.6264 (4 alternations; one per
+// wave 0.2310 / 0.6282)
+static int launch_count_pass(const SelCall& c, bool likely_lists) {
+    const bool two = c.L.T > 1;
+    const int which = two ? (likely_lists ? BT_CAP8 : BT_FULL8) : (likely_lists ? BT_CAP16 : BT_FULL);
+    const unsigned grid = (unsigned)(c.L.grid[BT_CNT] + c.L.grid[which]);
+    const auto k = two ? (c.al ? k_count_pass<true, 2> : k_count_pass<false, 2>)
+                       : (c.al ? k_count_pass<true, kSuper> : k_count_pass<false, kSuper>);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, c.s, c.vec, c.w, which, c.p, (int)c.L.grid[BT_CNT]);
+    DGC_LAUNCHED();
+    return DGC_OK;
+}
+
+// the list count alone; emit: it also writes the first-k payload (k_count_emit)
+static int launch_count_lists(const SelCall& c, const EmitOut* emit) {
+    if (emit)
+        hipLaunchKernelGGL(k_count_emit, dim3((unsigned)c.L.grid[BT_CNT]), dim3(kBlock), 0, c.s, c.vec, c.w, c.p,
+                           *emit);
+    else
+        hipLaunchKernelGGL(k_count_lists, dim3((unsigned)c.L.grid[BT_CNT]), dim3(kBlock), 0, c.s, c.vec, c.w, c.p);
+    DGC_LAUNCHED();
+    return DGC_OK;
+}
+
+// the full select pass alone
+static int launch_select_pass(const SelCall& c, bool likely_lists) {
+    const int which = likely_lists ? BT_CAP16 : BT_FULL;
+    hipLaunchKernelGGL(c.al ? k_select_pass<true> : k_select_pass<false>, dim3((unsigned)c.L.grid[which]),
+                       dim3(kBlock), 0, c.s, c.vec, c.w, which, c.p);
+    DGC_LAUNCHED();
+    return DGC_OK;
+}
+
+// The multi-threshold lowering. One tensor (the per-tensor path; the flat bucket chains
+// its lowering, k_chain_one): from the K1 lists first, then over vec if they do not
+// reach. A batch goes to vec at once: on per-step gradients a lowered threshold (0.8 t0)
+// sits below the lists almost always, and the list launch cost ResNet-50 6 us,
+// VGG-16-BN 4 (same box, 3 alternations).
+static int launch_lower(const SelCall& c) {
+    if (c.L.T == 1) {
+        hipLaunchKernelGGL(k_lower_lists, dim3((unsigned)c.L.grid[BT_SEG]), dim3(kBlock), 0, c.s, c.vec, c.w, c.p);
+        DGC_LAUNCHED();
+    }
+    hipLaunchKernelGGL((c.al ? k_lower_counts<true, 1> : k_lower_counts<false, 1>),
+                       dim3((unsigned)c.L.grid[BT_CAP4]), dim3(kBlock), 0, c.s, c.vec, c.w, c.p);
+    DGC_LAUNCHED();
+    return DGC_OK;
+}
+
+// The resample's nth_element path: gather the candidates, replay the introselect, emit
+// in its order. The gather launch also emits every other tensor's payload (the final
+// emit), and k_nth_select's last workgroup finishes the call (f).
+static int launch_resample(const SelCall& c, const EmitOut& o, FinishArgs f, const TestHooks& hooks) {
+    const Layout& L = c.L;
+    const uint32_t G = nth_global_groups(L.T, L.max_cand, hooks);
+    // An index-order engine whose replay runs on one workgroup (no global phase): the
+    // gather writes no queue — the sets read the keys, and the rare tied set that falls
+    // to the replay has k_nth_select rebuild its queue from them (one of the gather's
+    // four stores per candidate)
+    const bool no_queue = c.p.set_order && G <= 1;
+    EmitOut g = o;   // the K5 gather (+ every other tensor's payload)
+    g.queue = c.w.queue;
+    g.cand = c.w.cand_idx;
+    g.cval = c.w.cand_val;
+    g.ckey = c.w.cand_key;
+    g.no_queue = no_queue ? 1 : 0;
+    // K5s: an untied resample set in index order (the rest: the replay); with the wide
+    // emit, in its launch (k_emit_set)
+    const bool sets = c.p.set_order && L.grid[BT_SET] > 0;
+    if (sets && emit_is_wide(L, hooks)) {
+        hipLaunchKernelGGL(k_emit_wide_t<true>, dim3((unsigned)(L.grid[BT_GRP] + L.grid[BT_SET])), dim3(kGroupSegs),
+                           0, c.s, c.vec, c.w, g, o, (int32_t)L.grid[BT_GRP]);
+        DGC_LAUNCHED();
+    } else {
+        DGC_TRY(launch_emit(L, c.vec, c.w, g, hooks, c.s));
+        if (sets) {
+            hipLaunchKernelGGL(k_resample_set, dim3((unsigned)L.grid[BT_SET]), dim3(kScanThreads), 0, c.s, c.vec, c.w,
+                               o);
+            DGC_LAUNCHED();
+        }
+    }
+    // G > 1: the tensor's G workgroups run K5's global phase, then the extra ones emit
+    // the queue unless the replay's own workgroup does (every k <= kQueueFold).
+    // Parity tests: k5_multi runs the phase at any candidate count; k5_abort has the
+    // kernel expect one workgroup more than launched, so the residency consensus times
+    // out and the one-workgroup replay takes over.
+    const bool global_here = G > 1;
+    const bool emit_here = L.max_k <= kQueueFold;
+    const bool queue_here = !emit_here && global_here;
+    const int64_t min_run = hooks.k5_multi ? 0 : kNthGMinCand;
+    const uint32_t G_expected = hooks.k5_abort ? G + 1 : G;
+    f.on = 1;
+    hipLaunchKernelGGL(k_nth_select, dim3((unsigned)L.T, global_here ? G : 1u), dim3(kNthThreads), 0, c.s, c.vec,
+                       c.w, o, f, hooks.force_broken, emit_here ? 1 : 0, global_here ? 1 : 0, G,
+                       min_run, G_expected, queue_here ? 1 : 0, no_queue ? 1 : 0);
+    DGC_LAUNCHED();
+    if (!emit_here && !queue_here) {
+        hipLaunchKernelGGL(k_emit_queue, dim3((unsigned)L.grid[BT_QUEUE]), dim3(kBlock), 0, c.s, c.vec, c.w, o);
+        DGC_LAUNCHED();
+    }
+    return DGC_OK;
+}
+
+// The selection of every tensor (its K1 lists kept or not), from k_sel_init to the
+// payload: stream-ordered, and in DGC_SYNC_DEVICE mode with no host synchronisation.
 static int select_core(float* vec, float* mmt, const SelCfg& p, const Layout& L, void* values, void* indices,
                        int64_t* count_out, dgc_select_info* info, const SelWS& w, int keep_lists, int sync_mode,
                        float margin, int32_t* sink, int64_t* order_out, hipStream_t s) {
@@ -3373,209 +3493,29 @@ static int select_core(float* vec, float* mmt, const SelCfg& p, const Layout& L,
         hipLaunchKernelGGL(k_sel_init, dim3((unsigned)L.T), dim3(kScanThreads), 0, s, w, 0);
         DGC_LAUNCHED();
     }
-    const bool al = aligned16(vec);
+    const TestHooks hooks = test_hooks();
+    const SelCall c{vec, aligned16(vec), w, p, L, s};
+    const bool device = sync_mode == DGC_SYNC_DEVICE;
     // resample=True with max_iters <= kMaxLower: one multi-threshold pass replaces the lowers
     const bool lower_fast = p.resample && p.max_iters <= kMaxLower;
-    EmitOut o{p.update_memory ? vec : nullptr, (p.update_memory && p.masking) ? mmt : nullptr, values, indices,
-              p.vdtype, p.idtype, nullptr, nullptr, (int32_t)(p.update_memory == 2)};
+    const EmitOut o{p.update_memory ? vec : nullptr, (p.update_memory && p.masking) ? mmt : nullptr, values, indices,
+                    p.vdtype, p.idtype, nullptr, nullptr, (int32_t)(p.update_memory == 2)};
+    const FinishArgs fin{count_out, info, margin, (int32_t)(p.update_memory == 2), (int32_t)(p.masking != 0), 0,
+                         sink, 0u, order_out};
+    // a pass where either the lists or vec may serve: in one launch when the decisions
+    // stay on the device and the lowering is the one multi-threshold pass
+    const bool merge_ok = lower_fast && device;
+    auto pass_either = [&](bool likely_lists, const EmitOut* emit = nullptr) -> int {
+        if (merge_ok) return emit ? launch_count_emit_pass(c, *emit, likely_lists) : launch_count_pass(c, likely_lists);
+        DGC_TRY(launch_count_lists(c, emit));
+        return launch_select_pass(c, likely_lists);
+    };
     // the first list count of a one-tensor call also writes the first-k payload
     // (k_count_emit) when that emit would not mask and the payload starts at slot 0
-    const bool fuse = keep_lists && L.T == 1 && !L.tail_any && sync_mode == DGC_SYNC_DEVICE &&
-                      (p.update_memory == 2 || p.update_memory == 0) && !std::getenv("DGC_NO_COUNT_EMIT");
-    static const bool pass_split = std::getenv("DGC_PASS_SPLIT") != nullptr;
-    static const int pass_super = [] {
-        const char* e = std::getenv("DGC_PASS_SUPER");
-        const int v = e ? std::atoi(e) : 2;
-        return v == 1 || v == 2 ? v : kSuper;
-    }();
-    const bool merge_ok = lower_fast && sync_mode == DGC_SYNC_DEVICE && !pass_split;
-    auto pass = [&](int need, bool likely_lists, bool fused = false) -> int {
-        // one count pass at t_cur: lists when t_cur >= t_list, else the full select pass
-        // (both gated per tensor on the device); need: 1 = lists, 2 = full, 3 = either
-        // each count kernel's last workgroup per tensor takes the adaptation step
-        if (need == 3 && fused && merge_ok) {   // both in one launch (k_count_emit_pass)
-            const int which = likely_lists ? BT_CAP16 : BT_FULL;
-            const unsigned grid = (unsigned)(L.grid[BT_CNT] + L.grid[which]);
-            if (al)
-                hipLaunchKernelGGL(k_count_emit_pass<true>, dim3(grid), dim3(kBlock), 0, s, vec, w, p, o, which,
-                                   (int)L.grid[BT_CNT]);
-            else
-                hipLaunchKernelGGL(k_count_emit_pass<false>, dim3(grid), dim3(kBlock), 0, s, vec, w, p, o, which,
-                                   (int)L.grid[BT_CNT]);
-            DGC_LAUNCHED();
-            return DGC_OK;
-        }
-        if (need == 3 && !fused && merge_ok) {   // both in one launch (k_count_pass)
-            // a batch's full passes: two segments per wave (DGC_PASS_SUPER=1|4: one or
-            // kSuper, A/B). Measured (tools/pass_prof.py, ResNet-50): four per wave keep
-            // a working workgroup ~9 us on its list appends after 3 us of loads, one per
-            // wave ~3 us but 6289 workgroups enter over 10.7 us (the working ones hold
-            // the slots); two: 6 us each, all entered within 3.9 us, the pass ends at 15
-            // instead of 18 us — ResNet-50 0.2269 -> 0.2235 ms, VGG-16-BN 0.6275 -> 0.6264
-            // (4 alternations; one per wave 0.2310 / 0.6282)
-            const int sup = L.T > 1 ? pass_super : kSuper;
-            const int which = sup == 1 ? (likely_lists ? BT_CAP4 : BT_K1)
-                            : sup == 2 ? (likely_lists ? BT_CAP8 : BT_FULL8) : (likely_lists ? BT_CAP16 : BT_FULL);
-            const unsigned grid = (unsigned)(L.grid[BT_CNT] + L.grid[which]);
-            if (sup == 1 && al)
-                hipLaunchKernelGGL((k_count_pass<true, 1>), dim3(grid), dim3(kBlock), 0, s, vec, w, which, p,
-                                   (int)L.grid[BT_CNT]);
-            else if (sup == 1)
-                hipLaunchKernelGGL((k_count_pass<false, 1>), dim3(grid), dim3(kBlock), 0, s, vec, w, which, p,
-                                   (int)L.grid[BT_CNT]);
-            else if (sup == 2 && al)
-                hipLaunchKernelGGL((k_count_pass<true, 2>), dim3(grid), dim3(kBlock), 0, s, vec, w, which, p,
-                                   (int)L.grid[BT_CNT]);
-            else if (sup == 2)
-                hipLaunchKernelGGL((k_count_pass<false, 2>), dim3(grid), dim3(kBlock), 0, s, vec, w, which, p,
-                                   (int)L.grid[BT_CNT]);
-            else if (al)
-                hipLaunchKernelGGL((k_count_pass<true, kSuper>), dim3(grid), dim3(kBlock), 0, s, vec, w, which, p,
-                                   (int)L.grid[BT_CNT]);
-            else
-                hipLaunchKernelGGL((k_count_pass<false, kSuper>), dim3(grid), dim3(kBlock), 0, s, vec, w, which, p,
-                                   (int)L.grid[BT_CNT]);
-            DGC_LAUNCHED();
-            return DGC_OK;
-        }
-        if (need & 1) {
-            if (fused)
-                hipLaunchKernelGGL(k_count_emit, dim3((unsigned)L.grid[BT_CNT]), dim3(kBlock), 0, s, vec, w, p, o);
-            else
-                hipLaunchKernelGGL(k_count_lists, dim3((unsigned)L.grid[BT_CNT]), dim3(kBlock), 0, s, vec, w, p);
-            DGC_LAUNCHED();
-        }
-        if (need & 2) {
-            const int which = likely_lists ? BT_CAP16 : BT_FULL;
-            const unsigned grid = (unsigned)L.grid[which];
-            if (al)
-                hipLaunchKernelGGL(k_select_pass<true>, dim3(grid), dim3(kBlock), 0, s, vec, w, which, p);
-            else
-                hipLaunchKernelGGL(k_select_pass<false>, dim3(grid), dim3(kBlock), 0, s, vec, w, which, p);
-            DGC_LAUNCHED();
-        }
-        return DGC_OK;
-    };
-    // the lowering from the K1 lists first, then over vec if they do not reach: for one
-    // tensor (the per-tensor path; the flat bucket chains its lowering, k_chain_one). A
-    // batch goes to vec at once: on per-step gradients a lowered threshold (0.8 t0) sits
-    // below the lists almost always, and the list launch cost ResNet-50 6 us, VGG-16-BN 4
-    // (same box, 3 alternations); DGC_LOWER_LISTS=0/1 overrides
-    static const int lower_lists_env = [] {
-        const char* e = std::getenv("DGC_LOWER_LISTS");
-        return e ? (std::atoi(e) != 0 ? 1 : 0) : -1;
-    }();
-    const bool lower_lists = lower_lists_env >= 0 ? lower_lists_env == 1 : L.T == 1;
-    static const int lower_segs = std::getenv("DGC_LOWER_SEGS") && std::atoi(std::getenv("DGC_LOWER_SEGS")) == 2 ? 2 : 1;
-    auto lower = [&]() -> int {
-        if (lower_lists) {
-            hipLaunchKernelGGL(k_lower_lists, dim3((unsigned)L.grid[BT_SEG]), dim3(kBlock), 0, s, vec, w, p);
-            DGC_LAUNCHED();
-        }
-        // (DGC_LOWER_SEGS=2: two segments per wave over half the workgroups — A/B)
-        const bool two = lower_segs == 2;
-        const unsigned grid = (unsigned)L.grid[two ? BT_CAP8 : BT_CAP4];
-        if (two && al)
-            hipLaunchKernelGGL((k_lower_counts<true, 2>), dim3(grid), dim3(kBlock), 0, s, vec, w, p);
-        else if (two)
-            hipLaunchKernelGGL((k_lower_counts<false, 2>), dim3(grid), dim3(kBlock), 0, s, vec, w, p);
-        else if (al)
-            hipLaunchKernelGGL((k_lower_counts<true, 1>), dim3(grid), dim3(kBlock), 0, s, vec, w, p);
-        else
-            hipLaunchKernelGGL((k_lower_counts<false, 1>), dim3(grid), dim3(kBlock), 0, s, vec, w, p);
-        DGC_LAUNCHED();
-        return DGC_OK;
-    };
-    // DGC_K5_FORCE_BROKEN=1 (parity tests only): every replayed tensor takes the recovery
-    // of a broken global phase (k_nth_select), without a barrier actually timing out
-    const int force = std::getenv("DGC_K5_FORCE_BROKEN") ? 1 : 0;
-    static const float margin_max = [] {
-        const char* e = std::getenv("DGC_SPEC_MARGIN_MAX");
-        return e ? std::strtof(e, nullptr) : kSpecMarginMax;
-    }();
-    const FinishArgs fin{count_out, info, margin, (int32_t)(p.update_memory == 2), (int32_t)(p.masking != 0), 0,
-                         sink, 0u, order_out, margin_max};
-    bool finished = false;   // the payload count and records are written
-    // one tensor, device decisions, the lowering shortcut: the lowering and the count at
-    // the lowered threshold in one launch (k_chain_one); DGC_NO_CHAIN=1 (A/B runs)
-    // launches them one by one
-    static const bool no_chain = std::getenv("DGC_NO_CHAIN") != nullptr;
-    static const bool chain_batch = std::getenv("DGC_CHAIN_BATCH") != nullptr;   // (A/B: the batches too)
-    const bool chained = (L.T == 1 || chain_batch) && keep_lists && sync_mode == DGC_SYNC_DEVICE && lower_fast &&
-                         !no_chain;
-    EmitOut g = o;   // the K5 gather (+ every other tensor's payload)
-    g.queue = w.queue;
-    g.cand = w.cand_idx;
-    g.cval = w.cand_val;
-    g.ckey = w.cand_key;
-    // A/B switches (defaults measured): the one-workgroup limit of a K5s set,
-    // the replay's own emit for small k, the merged count pass, the lowering from lists
-    static const int64_t set_one_max = [] {
-        const char* e = std::getenv("DGC_SET_ONE");
-        return e ? std::max<int64_t>(std::atoll(e), 1) : kSetOneMax;
-    }();
-    static const bool queue_launch = std::getenv("DGC_QUEUE_LAUNCH") != nullptr;
-    const bool emit_here = !queue_launch && L.max_k <= kQueueFold;
-    auto resample_exact = [&]() -> int {
-        // nth_element path: gather candidates, replay the introselect, emit in its order.
-        // The gather launch also emits every other tensor's payload (the final emit).
-        const uint32_t G = nth_global_groups(L.T, L.max_cand);
-        // An index-order engine whose replay runs on one workgroup (no global phase): the
-        // gather writes no queue — the sets read the keys, and the rare tied set that
-        // falls to the replay has k_nth_select rebuild its queue from them (one of the
-        // gather's four stores per candidate; DGC_GATHER_QUEUE=1 writes it, A/B)
-        static const bool gather_queue = std::getenv("DGC_GATHER_QUEUE") != nullptr;
-        const bool no_queue = p.set_order && G <= 1 && !gather_queue;
-        g.no_queue = no_queue ? 1 : 0;
-        // K5s: an untied resample set in index order (the rest: the replay); with the
-        // wide emit, in its launch (k_emit_set; DGC_SET_SEPARATE=1: two launches, A/B)
-        static const bool set_separate = std::getenv("DGC_SET_SEPARATE") != nullptr;
-        const bool sets = p.set_order && L.grid[BT_SET] > 0;
-        if (sets && !set_separate && emit_is_wide(L)) {
-            hipLaunchKernelGGL(k_emit_wide_t<true>, dim3((unsigned)(L.grid[BT_GRP] + L.grid[BT_SET])),
-                               dim3(kGroupSegs), 0, s, vec, w, g, o, set_one_max, set_gmin(), (int32_t)L.grid[BT_GRP]);
-            DGC_LAUNCHED();
-        } else {
-            DGC_TRY(launch_emit(L, vec, w, g, s));
-            if (sets) {
-                hipLaunchKernelGGL(k_resample_set, dim3((unsigned)L.grid[BT_SET]), dim3(kScanThreads), 0, s, vec, w,
-                                   o, set_one_max, set_gmin());
-                DGC_LAUNCHED();
-            }
-        }
-        // DGC_K5_GLOBAL=multi: every range over several workgroups (parity); =abort: the
-        // kernel expects one workgroup more than launched, so the residency consensus
-        // times out and the one-workgroup replay takes over (the fallback's parity test)
-        const char* gforce = std::getenv("DGC_K5_GLOBAL");
-        const bool multi = gforce && (std::strcmp(gforce, "multi") == 0 || std::strcmp(gforce, "abort") == 0);
-        const bool abort = gforce && std::strcmp(gforce, "abort") == 0;
-        const int64_t min_run = multi ? 0 : kNthGMinCand;
-        const uint32_t G_expected = abort ? G + 1 : G;
-        static const bool nth_separate = std::getenv("DGC_NTH_SEPARATE") != nullptr;
-        const bool global_here = G > 1 && !nth_separate;
-        if (G > 1 && !global_here) {
-            hipLaunchKernelGGL(k_nth_global, dim3(G, (unsigned)L.T), dim3(kNthThreads), 0, s, w, G, min_run,
-                               G_expected);
-            DGC_LAUNCHED();
-        }
-        FinishArgs f = fin;
-        f.on = 1;   // k_nth_select's last workgroup finishes the call
-        // (DGC_QUEUE_LAUNCH=1 above: always k_emit_queue, A/B)
-        const bool queue_here = !emit_here && global_here && !queue_launch;
-        hipLaunchKernelGGL(k_nth_select, dim3((unsigned)L.T, global_here ? G : 1u), dim3(kNthThreads), 0, s, vec, w,
-                           o, G > 1 ? 1 : 0, f, force, emit_here ? 1 : 0, global_here ? 1 : 0, G, min_run, G_expected,
-                           queue_here ? 1 : 0, no_queue ? 1 : 0);
-        DGC_LAUNCHED();
-        finished = true;
-        if (!emit_here && !queue_here) {
-            hipLaunchKernelGGL(k_emit_queue, dim3((unsigned)L.grid[BT_QUEUE]), dim3(kBlock), 0, s, vec, w, o);
-            DGC_LAUNCHED();
-        }
-        return DGC_OK;
-    };
-    DGC_TRY(keep_lists ? pass(3, true, fuse) : pass(2, false));
-    bool emitted = false;   // the payload of every non-K5 tensor is written
-    if (sync_mode == DGC_SYNC_HOST) {
+    const bool fuse = keep_lists && L.T == 1 && !L.tail_any && device && (p.update_memory == 2 || p.update_memory == 0);
+    DGC_TRY(keep_lists ? pass_either(true, fuse ? &o : nullptr) : launch_select_pass(c, false));
+    bool resampled = false;   // launch_resample wrote every payload and finished the call
+    if (!device) {
         // read the decisions back and launch only what they need
         std::vector<SelState> hs(L.T);
         for (;;) {
@@ -3594,45 +3534,37 @@ static int select_core(float* vec, float* mmt, const SelCfg& p, const Layout& L,
             }
             if (all_done) break;
             if (any_lower) {
-                DGC_TRY(lower());   // picks t_cur on the device: either pass may follow
-                DGC_TRY(pass(3, false));
+                DGC_TRY(launch_lower(c));   // picks t_cur on the device: either pass may follow
+                DGC_TRY(pass_either(false));
             } else {
-                DGC_TRY(pass((any_list ? 1 : 0) | (any_full ? 2 : 0), false));
+                if (any_list) DGC_TRY(launch_count_lists(c, nullptr));
+                if (any_full) DGC_TRY(launch_select_pass(c, false));
             }
         }
-        bool any_resample = false;
-        for (const SelState& h : hs) any_resample |= h.branch == DGC_BRANCH_RESAMPLE;
-        if (any_resample) {   // k_nth_select serves both paths (K5, K5b)
-            DGC_TRY(resample_exact());
-            emitted = true;
-        }
+        for (const SelState& h : hs) resampled |= h.branch == DGC_BRANCH_RESAMPLE;
     } else if (L.adapt_any) {
         // every kernel below early-exits on a device flag when it is not needed
-        if (chained) {   // lower() and pass(3)'s count in one launch, then its full pass
+        if (L.T == 1 && keep_lists && lower_fast) {
+            // one tensor: the lowering and the count at the lowered threshold in one
+            // launch (k_chain_one), then its full pass
             const unsigned grid = (unsigned)std::min<int64_t>(
                 kCapBlocks, std::max({L.grid[BT_SEG], L.grid[BT_CAP4], L.grid[BT_CNT]}));
-            if (al)
-                hipLaunchKernelGGL(k_chain_one<true>, dim3(grid), dim3(kBlock), 0, s, vec, w, p);
-            else
-                hipLaunchKernelGGL(k_chain_one<false>, dim3(grid), dim3(kBlock), 0, s, vec, w, p);
+            hipLaunchKernelGGL(c.al ? k_chain_one<true> : k_chain_one<false>, dim3(grid), dim3(kBlock), 0, s, vec, w,
+                               p);
             DGC_LAUNCHED();
-            DGC_TRY(pass(2, true));
+            DGC_TRY(launch_select_pass(c, true));
         } else if (lower_fast) {
-            DGC_TRY(lower());
-            DGC_TRY(pass(3, true));
+            DGC_TRY(launch_lower(c));
+            DGC_TRY(pass_either(true));
         } else {
-            for (int i = 0; i < p.max_iters; ++i) DGC_TRY(pass(3, true));
+            for (int i = 0; i < p.max_iters; ++i) DGC_TRY(pass_either(true));
         }
-        if (p.resample) {
-            DGC_TRY(resample_exact());
-            emitted = true;
-        }
+        resampled = p.resample != 0;
     }
-    if (!emitted) DGC_TRY(launch_emit(L, vec, w, o, s));
-    if (!finished) {
-        hipLaunchKernelGGL(k_sel_finish, dim3(1), dim3(256), 0, s, w, fin);
-        DGC_LAUNCHED();
-    }
+    if (resampled) return launch_resample(c, o, fin, hooks);   // k_nth_select serves both paths (K5, K5b)
+    DGC_TRY(launch_emit(L, vec, w, o, hooks, s));
+    hipLaunchKernelGGL(k_sel_finish, dim3(1), dim3(256), 0, s, w, fin);
+    DGC_LAUNCHED();
     return DGC_OK;
 }
 
@@ -3713,10 +3645,8 @@ int kth_largest(const float* x, int64_t n, int64_t k, float* out, void* ws, size
 // three multi-block passes.
 static int thresholds(const SelWS& w, const Layout& L, const float* vec, hipStream_t s, int64_t ks1 = 0) {
     if (L.nsmall + L.nwins) {
-        // DGC_NO_WIN_HIST=1 (A/B runs): the window's keys only, not K1's histogram of them
-        static const int use_hist = std::getenv("DGC_NO_WIN_HIST") ? 0 : 1;
         hipLaunchKernelGGL(k_rs_small_multi, dim3((unsigned)(L.nsmall + L.nwins)), dim3(kScanThreads), 0, s, w, vec,
-                           ks1, L.nsmall, use_hist);
+                           ks1, L.nsmall);
         DGC_LAUNCHED();
     }
     if (L.grid[BT_SAMP] > 0) {
@@ -3724,16 +3654,10 @@ static int thresholds(const SelWS& w, const Layout& L, const float* vec, hipStre
             hipLaunchKernelGGL(k_rs_reset_samples, dim3((unsigned)L.T), dim3(kBlock), 0, s, w, ks1);
             DGC_LAUNCHED();
         }
-        // DGC_NO_RS_CHAIN=1 (A/B runs): the three passes as three launches
-        static const bool no_chain = std::getenv("DGC_NO_RS_CHAIN") != nullptr;
-        if (no_chain) {
-            DGC_TRY(radix_select_passes(SampleKeys{w, vec}, (int)L.grid[BT_SAMP], s));
-        } else {
-            const int grid = (int)L.grid[BT_SAMP];
-            hipLaunchKernelGGL(k_rs_passes<SampleKeys>, dim3((unsigned)std::min(grid, 1024)), dim3(kBlock), 0, s,
-                               SampleKeys{w, vec}, grid, (int)L.T);
-            DGC_LAUNCHED();
-        }
+        const int grid = (int)L.grid[BT_SAMP];
+        hipLaunchKernelGGL(k_rs_passes<SampleKeys>, dim3((unsigned)std::min(grid, 1024)), dim3(kBlock), 0, s,
+                           SampleKeys{w, vec}, grid, (int)L.T);
+        DGC_LAUNCHED();
     }
     return DGC_OK;
 }

@@ -21,7 +21,7 @@ golden resample steps, in order.
 
 The nth_element partition is written in the same data-parallel form the GPU kernel
 (K5: ``adam-compression_amd/csrc/introselect.hpp``, launched from ``csrc/select.hip``'s
-``k_nth_select`` / ``k_nth_global``) uses, so this file is also that kernel's
+``k_nth_select``, on one workgroup per tensor or several) uses, so this file is also that kernel's
 specification; ``partial_sort`` below is what K5b (``heap_select_wg`` in
 ``csrc/select.hip``) replays. One
 ``__unguarded_partition(first + 1, last, pivot = first)`` is, with P the pivot key:

@@ -56,7 +56,7 @@ def _sets():
 def test_batch_matches_per_tensor_oracle(label, shape, monkeypatch):
     """shape: the emit kernel (None: the library's choice — k_emit_wide for these few
     groups; "quarter": k_emit, the flat buckets' kernel, forced), or "k5multi": the
-    resample replay's global phase over several workgroups per tensor (k_nth_global);
+    resample replay's global phase over several workgroups per tensor (k_nth_select's extra workgroups);
     "topk": resample_order="topk" (every resample replays torch's order; the K5 shapes
     too) — otherwise DGCBatch's default "index" (an untied resample: the set). "+naninf": tensor "b"
     gets a NaN at one of its samples on step 1 (its threshold turns NaN, nothing of it

@@ -242,8 +242,8 @@ def test_resample_replays_torch_topk(L, case, k5, monkeypatch):
     """K5: the resample's indices are torch.topk(importance[indices], k, sorted=False)'s,
     IN ORDER (dgc/compression.py:134-137), so the payload bytes equal the reference's.
     k5: the global-memory phase (> 12288 candidates) over several co-resident
-    workgroups (k_nth_global; by default only for candidate capacities > 262144) or
-    inside the one-workgroup kernel."""
+    workgroups (k_nth_select's extra workgroups per tensor; by default only for candidate
+    capacities > 98304) or on the tensor's one replay workgroup."""
     monkeypatch.setenv("DGC_K5_GLOBAL", k5)
     name, n, ratio, kind, target = case
     attrs = O.attributes(n, ratio)

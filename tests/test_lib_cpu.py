@@ -136,6 +136,30 @@ def test_resample_replay_width_refusals_without_gpu(L):
         assert rc == 1 and b"null vec" in L.dgc_last_error(), (n, k, L.dgc_last_error())
 
 
+def test_environment_switches_are_the_documented_three():
+    """The native sources read exactly three environment variables, all in one function
+    (select.hip's test_hooks), and INTEGRATION.md names each: a switch nothing tests or
+    documents cannot grow back unnoticed."""
+    csrc = os.path.join(REPO, "adam-compression_amd", "csrc")
+    names, readers = set(), []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".hpp", ".cpp")):
+            continue
+        text = open(os.path.join(csrc, f)).read()
+        calls = re.findall(r"\bgetenv\s*\(\s*([^)]*?)\s*\)", text)
+        if calls:
+            readers.append(f)
+        for arg in calls:
+            m = re.fullmatch(r'"([^"]*)"', arg)
+            assert m, f"{f}: getenv({arg}) does not take a string literal"
+            names.add(m.group(1))
+    assert names == {"DGC_EMIT_SHAPE", "DGC_K5_GLOBAL", "DGC_K5_FORCE_BROKEN"}
+    assert readers == ["select.hip"]
+    doc = open(os.path.join(REPO, "INTEGRATION.md")).read()
+    for n in sorted(names):
+        assert n in doc, f"INTEGRATION.md does not mention {n}"
+
+
 def test_host_glue_tables_and_rebinding():
     """The batched optimizer's host glue (lib/_dgc_glue.so) on CPU tensors: the pointer
     table with its fallback positions (no gradient, misaligned, non-contiguous), the

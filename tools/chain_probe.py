@@ -1,7 +1,8 @@
 """Cost of the flat bucket's selection when the speculative lists MISS (every other
 step the gradient scale drops 20x, so the sampled threshold falls below the list
-threshold and the full passes run): ms per step over a few steps, for comparing the
-chained launch (k_chain_one) with the separate launches (DGC_NO_CHAIN=1).
+threshold and the full passes run): ms per step over a few steps, the lowering and its
+count in one chained launch (k_chain_one). To compare against an older library, run
+whole steps through tools/ab_bench.py.
 
   python tools/chain_probe.py [numel] [steps]
 """
@@ -38,7 +39,7 @@ def main():
         info = b.last_info()
         print(f"step {s}: {t[-1]:.3f} ms branch {info['branch']} full_passes {info['full_passes']} "
               f"recounts {info['recounts']}", flush=True)
-    print(f"mean {sum(t) / len(t):.3f} ms  (DGC_NO_CHAIN={os.environ.get('DGC_NO_CHAIN', '')})")
+    print(f"mean {sum(t) / len(t):.3f} ms")
 
 
 if __name__ == "__main__":
