@@ -29,13 +29,13 @@ namespace dgc {
 // for the grid-stride loop (tools/membench.hip). The sample bookkeeping is per
 // block: (q0, r0) = floor/mod(4*256b - start, stride) once, then a 32-bit divide
 // of the lane's small offset.
-template <bool NEST, bool ACC, bool SAMPLE>
+template <bool NEST, bool ACC, bool SAMPLE, int CLIP>
 __global__ void __launch_bounds__(kBlock)
 k_compensate4(const float4* __restrict__ g, float4* __restrict__ mmt, float4* __restrict__ vec,
-              float4* __restrict__ out, int64_t n4, float mom, SampleSpec sp, int wt) {
+              float4* __restrict__ out, int64_t n4, float mom, SampleSpec sp, int wt, ClipArg ca) {
     const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (v >= n4) return;
-    const float4 gv = ld_nt(g + v);
+    const float4 gv = clip4<CLIP>(ld_nt(g + v), clip_coef<CLIP>(ca, 0));
     float4 mv = ld_nt(mmt + v);
     float4 vv = ACC ? ld_nt(vec + v) : make_float4(0.f, 0.f, 0.f, 0.f);
     float4 ov;
@@ -68,15 +68,16 @@ k_compensate4(const float4* __restrict__ g, float4* __restrict__ mmt, float4* __
 }
 
 // Scalar path: any alignment, any stride; also used for the < 4-element tail.
-template <bool NEST, bool ACC, bool SAMPLE>
+template <bool NEST, bool ACC, bool SAMPLE, int CLIP>
 __global__ void __launch_bounds__(kBlock)
 k_compensate1(const float* __restrict__ g, float* __restrict__ mmt, float* __restrict__ vec,
-              float* __restrict__ out, int64_t begin, int64_t n, float mom, SampleSpec sp) {
+              float* __restrict__ out, int64_t begin, int64_t n, float mom, SampleSpec sp, ClipArg ca) {
+    const float cf = clip_coef<CLIP>(ca, 0);
     for (int64_t i = begin + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * kBlock) {
         float mv = mmt[i];
         float vv = ACC ? vec[i] : 0.f;
-        const float ov = comp1<NEST, ACC>(g[i], mv, vv, mom);
+        const float ov = comp1<NEST, ACC>(clip1<CLIP>(g[i], cf), mv, vv, mom);
         mmt[i] = mv;
         if (ACC)
             vec[i] = vv;
@@ -131,9 +132,9 @@ int sample_strided_launch(const float* vec, int64_t start, int64_t stride, int64
     return DGC_OK;
 }
 
-template <bool NEST, bool ACC>
+template <bool NEST, bool ACC, int CLIP>
 static int launch_comp(const float* g, float* m, float* v, float* o, int64_t n, float mom,
-                       SampleSpec sp, hipStream_t st) {
+                       SampleSpec sp, ClipArg ca, hipStream_t st) {
     const bool sample = sp.out != nullptr;
     const bool vec_ok = aligned16(g) && aligned16(m) && (ACC ? aligned16(v) : aligned16(o)) &&
                         (!sample || (sp.stride >= 4 && sp.stride < (1LL << 30)));
@@ -148,11 +149,11 @@ static int launch_comp(const float* g, float* m, float* v, float* o, int64_t n, 
             auto v4 = reinterpret_cast<float4*>(v);
             auto o4 = reinterpret_cast<float4*>(o);
             if (sample)
-                hipLaunchKernelGGL((k_compensate4<NEST, ACC, true>), dim3((unsigned)grid), dim3(kBlock), 0, st,
-                                   g4, m4, v4, o4, n4, mom, sp, (int)write_through(n));
+                hipLaunchKernelGGL((k_compensate4<NEST, ACC, true, CLIP>), dim3((unsigned)grid), dim3(kBlock), 0, st,
+                                   g4, m4, v4, o4, n4, mom, sp, (int)write_through(n), ca);
             else
-                hipLaunchKernelGGL((k_compensate4<NEST, ACC, false>), dim3((unsigned)grid), dim3(kBlock), 0, st,
-                                   g4, m4, v4, o4, n4, mom, sp, (int)write_through(n));
+                hipLaunchKernelGGL((k_compensate4<NEST, ACC, false, CLIP>), dim3((unsigned)grid), dim3(kBlock), 0, st,
+                                   g4, m4, v4, o4, n4, mom, sp, (int)write_through(n), ca);
             DGC_LAUNCHED();
         }
         done = n4 * 4;
@@ -160,11 +161,11 @@ static int launch_comp(const float* g, float* m, float* v, float* o, int64_t n, 
     if (done < n) {
         const int grid = grid_for(n - done);
         if (sample)
-            hipLaunchKernelGGL((k_compensate1<NEST, ACC, true>), dim3(grid), dim3(kBlock), 0, st,
-                               g, m, v, o, done, n, mom, sp);
+            hipLaunchKernelGGL((k_compensate1<NEST, ACC, true, CLIP>), dim3(grid), dim3(kBlock), 0, st,
+                               g, m, v, o, done, n, mom, sp, ca);
         else
-            hipLaunchKernelGGL((k_compensate1<NEST, ACC, false>), dim3(grid), dim3(kBlock), 0, st,
-                               g, m, v, o, done, n, mom, sp);
+            hipLaunchKernelGGL((k_compensate1<NEST, ACC, false, CLIP>), dim3(grid), dim3(kBlock), 0, st,
+                               g, m, v, o, done, n, mom, sp, ca);
         DGC_LAUNCHED();
     }
     return DGC_OK;
@@ -249,9 +250,9 @@ k_compensate_wire(const void* __restrict__ src, float* __restrict__ mmt, float* 
 // gradients (a one-rank exchange: nothing to gather for an allreduce), mmt and out at
 // the tensors' offsets of two flat buffers; ROUND16: each gradient rounded to fp16 and
 // back first (the fp16 wire's cast and decompress's widening).
-template <bool NEST, bool ROUND16>
+template <bool NEST, bool ROUND16, int CLIP>
 __global__ void __launch_bounds__(kBlock) k_compensate_mt(MtChunk c, float* __restrict__ mmt, float* __restrict__ out,
-                                                          float mom) {
+                                                          float mom, ClipArg ca, int t0) {
     int lo = 0, hi = c.count - 1;
     const int b = (int)blockIdx.x;
     while (lo < hi) {
@@ -261,12 +262,13 @@ __global__ void __launch_bounds__(kBlock) k_compensate_mt(MtChunk c, float* __re
     const int t = lo;
     const float* __restrict__ src = c.src[t];
     const int64_t n = c.n[t], off = c.off[t];
+    const float cf = clip_coef<CLIP>(ca, t0 + t);
     const int64_t e0 = ((int64_t)(b - c.bstart[t]) * kBlock) * kMtPerThread + threadIdx.x;
 #pragma unroll
     for (int j = 0; j < kMtPerThread; ++j) {
         const int64_t e = e0 + (int64_t)j * kBlock;
         if (e >= n) break;
-        const float g = ROUND16 ? f16_to_f32(f32_to_f16(src[e])) : src[e];
+        const float g = clip1<CLIP>(ROUND16 ? f16_to_f32(f32_to_f16(src[e])) : src[e], cf);
         float m = mmt[off + e], v = 0.f;
         const float o = comp1<NEST, false>(g, m, v, mom);
         mmt[off + e] = m;
@@ -295,11 +297,31 @@ static int mt_chunk(const float* const* srcs, const int64_t* numels, const int64
     return DGC_OK;
 }
 
+// The clip kinds of a K1 call: SCALE needs the coefficient table, CLAMP a table or a value.
+static int clip_check(int32_t kind, const float* clip, const char* who) {
+    if (!clip_kind_ok(kind)) DGC_FAIL(DGC_ERR_INVALID, "%s: clip kind %d", who, (int)kind);
+    if (kind == DGC_CLIP_SCALE && !clip) DGC_FAIL(DGC_ERR_INVALID, "%s: DGC_CLIP_SCALE needs the coefficient table", who);
+    return DGC_OK;
+}
+
+template <bool NEST, bool ROUND16>
+static void launch_mt(int32_t kind, dim3 gd, dim3 bd, hipStream_t st, const MtChunk& c, float* mmt, float* out,
+                      float mom, ClipArg ca, int t0) {
+    if (kind == DGC_CLIP_SCALE)
+        hipLaunchKernelGGL((k_compensate_mt<NEST, ROUND16, DGC_CLIP_SCALE>), gd, bd, 0, st, c, mmt, out, mom, ca, t0);
+    else if (kind == DGC_CLIP_CLAMP)
+        hipLaunchKernelGGL((k_compensate_mt<NEST, ROUND16, DGC_CLIP_CLAMP>), gd, bd, 0, st, c, mmt, out, mom, ca, t0);
+    else
+        hipLaunchKernelGGL((k_compensate_mt<NEST, ROUND16, DGC_CLIP_NONE>), gd, bd, 0, st, c, mmt, out, mom, ca, t0);
+}
+
 int compensate_multi(const float* const* srcs, const int64_t* numels, const int64_t* offsets, int32_t count,
-                     int32_t round_to, float* mmt, float* out, float mom, bool nesterov, hipStream_t st) {
+                     int32_t round_to, float* mmt, float* out, float mom, bool nesterov, int32_t clip_kind,
+                     ClipArg ca, hipStream_t st) {
     if (count < 0 || (count > 0 && (!srcs || !numels || !offsets || !mmt || !out)))
         DGC_FAIL(DGC_ERR_INVALID, "dgc_compensate_multi: null argument");
     if (round_to != DGC_F32 && round_to != DGC_F16) DGC_FAIL(DGC_ERR_DTYPE, "dgc_compensate_multi: round_to");
+    DGC_TRY(clip_check(clip_kind, ca.tab, "dgc_compensate_multi"));
     for (int32_t t0 = 0; t0 < count; t0 += kMtMax) {
         MtChunk c;
         int64_t blocks;
@@ -307,11 +329,11 @@ int compensate_multi(const float* const* srcs, const int64_t* numels, const int6
         if (blocks == 0) continue;
         const dim3 gd((unsigned)blocks), bd(kBlock);
         if (nesterov) {
-            if (round_to == DGC_F16) hipLaunchKernelGGL((k_compensate_mt<true, true>), gd, bd, 0, st, c, mmt, out, mom);
-            else hipLaunchKernelGGL((k_compensate_mt<true, false>), gd, bd, 0, st, c, mmt, out, mom);
+            if (round_to == DGC_F16) launch_mt<true, true>(clip_kind, gd, bd, st, c, mmt, out, mom, ca, t0);
+            else launch_mt<true, false>(clip_kind, gd, bd, st, c, mmt, out, mom, ca, t0);
         } else {
-            if (round_to == DGC_F16) hipLaunchKernelGGL((k_compensate_mt<false, true>), gd, bd, 0, st, c, mmt, out, mom);
-            else hipLaunchKernelGGL((k_compensate_mt<false, false>), gd, bd, 0, st, c, mmt, out, mom);
+            if (round_to == DGC_F16) launch_mt<false, true>(clip_kind, gd, bd, st, c, mmt, out, mom, ca, t0);
+            else launch_mt<false, false>(clip_kind, gd, bd, st, c, mmt, out, mom, ca, t0);
         }
         DGC_LAUNCHED();
     }
@@ -485,10 +507,20 @@ int compensate_ranks(const void* src, int32_t dtype, int32_t world, int64_t rank
     return DGC_OK;
 }
 
-int compensate(const float* grad, float* mmt, float* vec, float* out, int64_t n, float momentum,
-               bool nesterov, bool accumulate, float* samples, int64_t s_start, int64_t s_stride,
-               int64_t s_count, hipStream_t st) {
+template <bool NEST, bool ACC>
+static int launch_comp_kind(int32_t kind, const float* g, float* m, float* v, float* o, int64_t n, float mom,
+                            SampleSpec sp, ClipArg ca, hipStream_t st) {
+    if (kind == DGC_CLIP_SCALE) return launch_comp<NEST, ACC, DGC_CLIP_SCALE>(g, m, v, o, n, mom, sp, ca, st);
+    if (kind == DGC_CLIP_CLAMP) return launch_comp<NEST, ACC, DGC_CLIP_CLAMP>(g, m, v, o, n, mom, sp, ca, st);
+    return launch_comp<NEST, ACC, DGC_CLIP_NONE>(g, m, v, o, n, mom, sp, ca, st);
+}
+
+// K1 with the gradient clipped as it is loaded (ca.tab points at this tensor's coefficient).
+int compensate_clip(const float* grad, float* mmt, float* vec, float* out, int64_t n, float momentum,
+                    bool nesterov, bool accumulate, float* samples, int64_t s_start, int64_t s_stride,
+                    int64_t s_count, int32_t clip_kind, ClipArg ca, hipStream_t st) {
     if (n < 0) DGC_FAIL(DGC_ERR_INVALID, "dgc_compensate: n < 0");
+    DGC_TRY(clip_check(clip_kind, ca.tab, "dgc_compensate"));
     if (n == 0) return DGC_OK;
     if (!grad || !mmt) DGC_FAIL(DGC_ERR_INVALID, "dgc_compensate: null grad/mmt");
     if (accumulate && !vec) DGC_FAIL(DGC_ERR_INVALID, "dgc_compensate: accumulate needs vec");
@@ -505,8 +537,8 @@ int compensate(const float* grad, float* mmt, float* vec, float* out, int64_t n,
         sp = SampleSpec{samples, s_start, s_stride, s_count, 1.0 / (double)s_stride, 1.0f / (float)s_stride};
         if (s_stride < 4) {
             // tiny strides (sample_ratio >= 0.25): unfused, samples read back after the pass
-            DGC_TRY(compensate(grad, mmt, vec, out, n, momentum, nesterov, accumulate, nullptr, 0,
-                               1, 0, st));
+            DGC_TRY(compensate_clip(grad, mmt, vec, out, n, momentum, nesterov, accumulate, nullptr, 0,
+                                    1, 0, clip_kind, ca, st));
             const int grid = grid_for(s_count);
             hipLaunchKernelGGL(k_sample_strided, dim3(grid), dim3(kBlock), 0, st, vec, s_start,
                                s_stride, s_count, samples);
@@ -515,10 +547,17 @@ int compensate(const float* grad, float* mmt, float* vec, float* out, int64_t n,
         }
     }
     if (nesterov)
-        return accumulate ? launch_comp<true, true>(grad, mmt, vec, out, n, momentum, sp, st)
-                          : launch_comp<true, false>(grad, mmt, vec, out, n, momentum, sp, st);
-    return accumulate ? launch_comp<false, true>(grad, mmt, vec, out, n, momentum, sp, st)
-                      : launch_comp<false, false>(grad, mmt, vec, out, n, momentum, sp, st);
+        return accumulate ? launch_comp_kind<true, true>(clip_kind, grad, mmt, vec, out, n, momentum, sp, ca, st)
+                          : launch_comp_kind<true, false>(clip_kind, grad, mmt, vec, out, n, momentum, sp, ca, st);
+    return accumulate ? launch_comp_kind<false, true>(clip_kind, grad, mmt, vec, out, n, momentum, sp, ca, st)
+                      : launch_comp_kind<false, false>(clip_kind, grad, mmt, vec, out, n, momentum, sp, ca, st);
+}
+
+int compensate(const float* grad, float* mmt, float* vec, float* out, int64_t n, float momentum,
+               bool nesterov, bool accumulate, float* samples, int64_t s_start, int64_t s_stride,
+               int64_t s_count, hipStream_t st) {
+    return compensate_clip(grad, mmt, vec, out, n, momentum, nesterov, accumulate, samples, s_start, s_stride,
+                           s_count, DGC_CLIP_NONE, ClipArg{nullptr, 0.f}, st);
 }
 
 }  // namespace dgc
@@ -570,7 +609,24 @@ extern "C" int dgc_compensate_multi(const float* const* srcs, const int64_t* num
                                     int32_t count, int32_t round_to, float* mmt, float* out, float momentum,
                                     int32_t nesterov, void* stream) {
     return dgc::compensate_multi(srcs, numels, offsets, count, round_to, mmt, out, momentum, nesterov != 0,
-                                 static_cast<hipStream_t>(stream));
+                                 DGC_CLIP_NONE, dgc::ClipArg{nullptr, 0.f}, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int dgc_compensate_multi_clip(const float* const* srcs, const int64_t* numels, const int64_t* offsets,
+                                         int32_t count, int32_t round_to, float* mmt, float* out, float momentum,
+                                         int32_t nesterov, int32_t clip_kind, const float* clip, float clip_value,
+                                         void* stream) {
+    return dgc::compensate_multi(srcs, numels, offsets, count, round_to, mmt, out, momentum, nesterov != 0,
+                                 clip_kind, dgc::ClipArg{clip, clip_value}, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int dgc_compensate_clip(const float* grad, float* mmt, float* vec, float* out, int64_t n, float momentum,
+                                   int32_t nesterov, int32_t accumulate, float* samples, int64_t sample_start,
+                                   int64_t sample_stride, int64_t num_samples, int32_t clip_kind, const float* clip,
+                                   float clip_value, void* stream) {
+    return dgc::compensate_clip(grad, mmt, vec, out, n, momentum, nesterov != 0, accumulate != 0, samples,
+                                sample_start, sample_stride, num_samples, clip_kind, dgc::ClipArg{clip, clip_value},
+                                static_cast<hipStream_t>(stream));
 }
 
 extern "C" int dgc_compensate_wire(const void* src, int32_t src_dtype, int32_t round_to, float* mmt, float* out,

@@ -409,6 +409,38 @@ __device__ __forceinline__ float comp1(float g, float& m, float& v, float mom) {
     }
     return m;
 }
+
+// Local gradient clipping applied to a gradient element as K1 loads it
+// (dgc/clip_grad.py:10-42 run as DGCSGDMemory.gradient_clipping, dgc/memory.py:52-53).
+// The coefficient of tensor t is tab[t], or `value` when tab is null (a fixed clamp).
+//   SCALE: `if clip_coef < 1: grad.mul_(clip_coef)` — one rounding; a NaN coefficient
+//          compares false and leaves the gradient alone.
+//   CLAMP: `grad.clamp_(min=-c, max=c)` — a NaN element stays NaN, a NaN bound gives NaN.
+struct ClipArg {
+    const float* tab;
+    float value;
+};
+
+__host__ __device__ inline bool clip_kind_ok(int kind) { return kind >= DGC_CLIP_NONE && kind <= DGC_CLIP_CLAMP; }
+
+template <int CLIP>
+__device__ __forceinline__ float clip_coef(const ClipArg& ca, int t) {
+    if (CLIP == DGC_CLIP_NONE) return 0.f;
+    return ca.tab ? ca.tab[t] : ca.value;
+}
+
+template <int CLIP>
+__device__ __forceinline__ float clip1(float g, float c) {
+    if (CLIP == DGC_CLIP_SCALE) return c < 1.f ? __fmul_rn(g, c) : g;
+    if (CLIP == DGC_CLIP_CLAMP) return c != c ? c : (g != g ? g : fminf(fmaxf(g, -c), c));
+    return g;
+}
+
+template <int CLIP>
+__device__ __forceinline__ float4 clip4(float4 g, float c) {
+    if (CLIP == DGC_CLIP_NONE) return g;
+    return make_float4(clip1<CLIP>(g.x, c), clip1<CLIP>(g.y, c), clip1<CLIP>(g.z, c), clip1<CLIP>(g.w, c));
+}
 // ---------------------------------------------------------------- error flags
 // A flag the host polls without synchronising (an engine's pinned status sink) or a
 // device int32: every writer stores the same constant — idempotent, so no

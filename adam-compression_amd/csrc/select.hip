@@ -643,10 +643,12 @@ static int mask_flush(float* vec, float* mmt, const Layout& L, const SelWS& w, h
 // ONE (a one-tensor call): the tensor's tables ride in the arguments (ot) — block 0
 // writes them into the workspace for the kernels after K1, which replaces a k_put_one
 // launch before every K1 (and its wait) — and the sample start in sc.
-template <bool NEST, bool ONE>
+// CLIP: the gradient clipped as it is loaded (dgc_common.hpp clip1), tensor t's
+// coefficient from ca; DGC_CLIP_NONE compiles to the unclipped kernel.
+template <bool NEST, bool ONE, int CLIP>
 __global__ void __launch_bounds__(kBlock)
 k_compensate_list(const float* __restrict__ g_flat, float* __restrict__ mmt_flat, float* __restrict__ vec_flat,
-                  float mom, SelWS w, StartChunk sc, int wt, OneTable ot) {
+                  float mom, SelWS w, StartChunk sc, int wt, OneTable ot, ClipArg ca) {
     const int t = ONE ? 0 : task(w, BT_K1, blockIdx.x);
     const TDesc d = ONE ? ot.d : w.td[t];   // by value: stores below cannot alias it
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -693,11 +695,12 @@ k_compensate_list(const float* __restrict__ g_flat, float* __restrict__ mmt_flat
     int64_t q0 = 0, r0 = 0;
     if (sample) floor_divmod_fast(ls * kSeg - start, d.stride, d.inv_stride, q0, r0);
     float4 gv[kSegTiles], mv[kSegTiles], vv[kSegTiles];
+    const float cf = clip_coef<CLIP>(ca, t);
 #pragma unroll
     for (int u = 0; u < kSegTiles; ++u) {
         const int64_t v = ls * (kSeg / 4) + u * 64 + lane;
         if (v < n4) {
-            gv[u] = sc.ptrs && 4 * v + 3 >= n ? ld_tail4(gsrc, 4 * v, n) : ld_nt(g + v);
+            gv[u] = clip4<CLIP>(sc.ptrs && 4 * v + 3 >= n ? ld_tail4(gsrc, 4 * v, n) : ld_nt(g + v), cf);
             mv[u] = ld_nt(mmt + v);
             vv[u] = ld_nt(vec + v);
         }
@@ -3666,6 +3669,9 @@ static int thresholds(const SelWS& w, const Layout& L, const float* vec, hipStre
 int compensate(const float* grad, float* mmt, float* vec, float* out, int64_t n, float momentum,
                bool nesterov, bool accumulate, float* samples, int64_t s_start, int64_t s_stride,
                int64_t s_count, hipStream_t st);
+int compensate_clip(const float* grad, float* mmt, float* vec, float* out, int64_t n, float momentum,
+                    bool nesterov, bool accumulate, float* samples, int64_t s_start, int64_t s_stride,
+                    int64_t s_count, int32_t clip_kind, ClipArg ca, hipStream_t st);
 int sample_strided_launch(const float* vec, int64_t start, int64_t stride, int64_t count, float* out,
                           hipStream_t s);
 
@@ -3698,10 +3704,28 @@ static int one_ws(const dgc_select_params* p, int64_t s_start, int64_t s_stride,
 }
 
 // K1 (+ fused strided sample + speculative candidate lists at spec[0]).
+// clip_kind / ca: the gradient clipped as K1 loads it (dgc_compress_begin_clip).
+template <bool NEST, bool ONE, typename... Args>
+static void launch_k1(int32_t clip_kind, dim3 gd, hipStream_t s, Args... args) {
+    if (clip_kind == DGC_CLIP_SCALE)
+        hipLaunchKernelGGL((k_compensate_list<NEST, ONE, DGC_CLIP_SCALE>), gd, dim3(kBlock), 0, s, args...);
+    else if (clip_kind == DGC_CLIP_CLAMP)
+        hipLaunchKernelGGL((k_compensate_list<NEST, ONE, DGC_CLIP_CLAMP>), gd, dim3(kBlock), 0, s, args...);
+    else
+        hipLaunchKernelGGL((k_compensate_list<NEST, ONE, DGC_CLIP_NONE>), gd, dim3(kBlock), 0, s, args...);
+}
+
+static int k1_clip_check(int32_t kind, const float* clip, const char* who) {
+    if (!clip_kind_ok(kind)) DGC_FAIL(DGC_ERR_INVALID, "%s: clip kind %d", who, (int)kind);
+    if (kind == DGC_CLIP_SCALE && !clip) DGC_FAIL(DGC_ERR_INVALID, "%s: DGC_CLIP_SCALE needs the coefficient table", who);
+    return DGC_OK;
+}
+
 int compress_begin(const float* grad, float* mmt, float* vec, float momentum, bool nesterov, int64_t s_start,
                    int64_t s_stride, const dgc_select_params* p, float* spec, void* ws, size_t ws_bytes,
-                   hipStream_t s) {
+                   hipStream_t s, int32_t clip_kind = DGC_CLIP_NONE, ClipArg ca = ClipArg{nullptr, 0.f}) {
     DGC_TRY(compress_check(p, nullptr, nullptr, s_start, s_stride, 1, false));
+    DGC_TRY(k1_clip_check(clip_kind, ca.tab, "dgc_compress"));
     if (!grad || !mmt || !vec) DGC_FAIL(DGC_ERR_INVALID, "dgc_compress: null grad/mmt/vec");
     Layout L;
     SelWS w;
@@ -3716,8 +3740,8 @@ int compress_begin(const float* grad, float* mmt, float* vec, float momentum, bo
         hipLaunchKernelGGL(k_put_one, dim3(1), dim3(64), 0, s, w, ot);
         DGC_LAUNCHED();
         DGC_TRY(mask_flush(vec, mmt, L, w, s));   // a deferring finish left its masking to K1
-        DGC_TRY(compensate(grad, mmt, vec, nullptr, n, momentum, nesterov, true, sampled ? w.samples : nullptr,
-                           s_start, s_stride, cnt, s));
+        DGC_TRY(compensate_clip(grad, mmt, vec, nullptr, n, momentum, nesterov, true, sampled ? w.samples : nullptr,
+                                s_start, s_stride, cnt, clip_kind, ca, s));
         hipLaunchKernelGGL(k_no_lists, dim3(1), dim3(64), 0, s, w);
         DGC_LAUNCHED();
         return DGC_OK;
@@ -3727,12 +3751,11 @@ int compress_begin(const float* grad, float* mmt, float* vec, float momentum, bo
         StartChunk one{};   // the start (and the tables, ot) in the arguments: no k_put_one
         one.count = 1;
         one.start[0] = ot.start;
+        const dim3 gd((unsigned)L.grid[BT_K1]);
         if (nesterov)
-            hipLaunchKernelGGL((k_compensate_list<true, true>), dim3((unsigned)L.grid[BT_K1]), dim3(kBlock), 0, s,
-                               grad, mmt, vec, momentum, w, one, (int)write_through(n), ot);
+            launch_k1<true, true>(clip_kind, gd, s, grad, mmt, vec, momentum, w, one, (int)write_through(n), ot, ca);
         else
-            hipLaunchKernelGGL((k_compensate_list<false, true>), dim3((unsigned)L.grid[BT_K1]), dim3(kBlock), 0, s,
-                               grad, mmt, vec, momentum, w, one, (int)write_through(n), ot);
+            launch_k1<false, true>(clip_kind, gd, s, grad, mmt, vec, momentum, w, one, (int)write_through(n), ot, ca);
         DGC_LAUNCHED();
     } else {
         hipLaunchKernelGGL(k_put_one, dim3(1), dim3(64), 0, s, w, ot);
@@ -3740,8 +3763,8 @@ int compress_begin(const float* grad, float* mmt, float* vec, float momentum, bo
     }
     if (n & 3) {   // scalar tail (< 4 elements) incl. its samples; its segment is marked spilled
         const int64_t done = (n / 4) * 4;
-        DGC_TRY(compensate(grad + done, mmt + done, vec + done, nullptr, n - done, momentum, nesterov, true, nullptr,
-                           0, 1, 0, s));
+        DGC_TRY(compensate_clip(grad + done, mmt + done, vec + done, nullptr, n - done, momentum, nesterov, true,
+                                nullptr, 0, 1, 0, clip_kind, ca, s));
         if (sampled) {
             // samples in the tail: start + q*stride >= done
             const int64_t q_first = done >= s_start ? ceil_div(done - s_start, s_stride) : 0;
@@ -3887,10 +3910,12 @@ static int batch_ws(const dgc_batch_desc* b, void* ws, size_t ws_bytes, const ch
 // gradients from the flat buffer (grads == null) or from a host table of T device
 // pointers (grads[t]: numel[t] contiguous floats, 16-B aligned).
 int batch_compress_begin(const dgc_batch_desc* b, const float* grad, const float* const* grads, float* mmt,
-                         float* vec, const int64_t* starts, void* ws, size_t ws_bytes, hipStream_t s) {
+                         float* vec, const int64_t* starts, void* ws, size_t ws_bytes, hipStream_t s,
+                         int32_t clip_kind = DGC_CLIP_NONE, ClipArg ca = ClipArg{nullptr, 0.f}) {
     Layout L;
     std::vector<TDesc> td;
     SelWS w;
+    DGC_TRY(k1_clip_check(clip_kind, ca.tab, "dgc_batch_compress"));
     DGC_TRY(batch_ws(b, ws, ws_bytes, "dgc_batch_compress", L, td, w));
     if ((!grad && !grads) || !mmt || !vec || !starts) DGC_FAIL(DGC_ERR_INVALID, "dgc_batch_compress: null pointer");
     if ((grad && !aligned16(grad)) || !aligned16(mmt) || !aligned16(vec))
@@ -3926,12 +3951,13 @@ int batch_compress_begin(const dgc_batch_desc* b, const float* grad, const float
         }
     }
     if (L.grid[BT_K1] > 0x7FFFFFFFLL) DGC_FAIL(DGC_ERR_INVALID, "dgc_batch_compress: too many segments");
+    const dim3 gd((unsigned)L.grid[BT_K1]);
     if (b->nesterov)
-        hipLaunchKernelGGL((k_compensate_list<true, false>), dim3((unsigned)L.grid[BT_K1]), dim3(kBlock), 0, s, grad,
-                           mmt, vec, b->momentum, w, arg, (int)write_through(L.nseg * kSeg), OneTable{});
+        launch_k1<true, false>(clip_kind, gd, s, grad, mmt, vec, b->momentum, w, arg,
+                               (int)write_through(L.nseg * kSeg), OneTable{}, ca);
     else
-        hipLaunchKernelGGL((k_compensate_list<false, false>), dim3((unsigned)L.grid[BT_K1]), dim3(kBlock), 0, s, grad,
-                           mmt, vec, b->momentum, w, arg, (int)write_through(L.nseg * kSeg), OneTable{});
+        launch_k1<false, false>(clip_kind, gd, s, grad, mmt, vec, b->momentum, w, arg,
+                                (int)write_through(L.nseg * kSeg), OneTable{}, ca);
     DGC_LAUNCHED();
     return DGC_OK;
 }
@@ -4132,6 +4158,31 @@ extern "C" int dgc_batch_compress_begin_ptrs(const dgc_batch_desc* batch, const 
     if (!grads) DGC_FAIL(DGC_ERR_INVALID, "dgc_batch_compress_begin_ptrs: null gradient table");
     return dgc::batch_compress_begin(batch, nullptr, grads, mmt, vec, sample_starts, ws, ws_bytes,
                                      static_cast<hipStream_t>(stream));
+}
+
+extern "C" int dgc_compress_begin_clip(const float* grad, float* mmt, float* vec, float momentum, int32_t nesterov,
+                                       int64_t sample_start, int64_t sample_stride, const dgc_select_params* params,
+                                       const float* spec_threshold, int32_t clip_kind, const float* clip,
+                                       float clip_value, void* ws, size_t ws_bytes, void* stream) {
+    return dgc::compress_begin(grad, mmt, vec, momentum, nesterov != 0, sample_start, sample_stride, params,
+                               const_cast<float*>(spec_threshold), ws, ws_bytes, static_cast<hipStream_t>(stream),
+                               clip_kind, dgc::ClipArg{clip, clip_value});
+}
+
+extern "C" int dgc_batch_compress_begin_clip(const dgc_batch_desc* batch, const float* grad, float* mmt, float* vec,
+                                             const int64_t* sample_starts, int32_t clip_kind, const float* clip,
+                                             float clip_value, void* ws, size_t ws_bytes, void* stream) {
+    return dgc::batch_compress_begin(batch, grad, nullptr, mmt, vec, sample_starts, ws, ws_bytes,
+                                     static_cast<hipStream_t>(stream), clip_kind, dgc::ClipArg{clip, clip_value});
+}
+
+extern "C" int dgc_batch_compress_begin_ptrs_clip(const dgc_batch_desc* batch, const float* const* grads, float* mmt,
+                                                  float* vec, const int64_t* sample_starts, int32_t clip_kind,
+                                                  const float* clip, float clip_value, void* ws, size_t ws_bytes,
+                                                  void* stream) {
+    if (!grads) DGC_FAIL(DGC_ERR_INVALID, "dgc_batch_compress_begin_ptrs: null gradient table");
+    return dgc::batch_compress_begin(batch, nullptr, grads, mmt, vec, sample_starts, ws, ws_bytes,
+                                     static_cast<hipStream_t>(stream), clip_kind, dgc::ClipArg{clip, clip_value});
 }
 
 extern "C" int dgc_batch_compress_finish(const dgc_batch_desc* batch, float* mmt, float* vec, void* payload,

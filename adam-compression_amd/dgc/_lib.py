@@ -239,6 +239,20 @@ _SIGNATURES = {
     "dgc_widen16": (ctypes.c_int, [_P, _P, _I64, _I32, _P]),
     "dgc_decompress16": (ctypes.c_int, [_P, _I32, _P, _I32, ctypes.POINTER(ctypes.c_int64), _I32, _P, _I32, _I64,
                                         _F, _P, _P]),
+    "dgc_grad_stats_workspace": (_SZ, [ctypes.POINTER(_I64), _I32]),
+    "dgc_grad_stats": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.POINTER(_I64), _I32, _I32, _I32, _P, _P, _SZ, _P]),
+    "dgc_clip_coefs": (ctypes.c_int, [_P, _I32, _I32, _F, _P, _P]),
+    "dgc_clip_apply": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.POINTER(_I64), _I32, _I32, _P, _F, _P]),
+    "dgc_compensate_clip": (ctypes.c_int, [_P, _P, _P, _P, _I64, _F, _I32, _I32, _P, _I64, _I64, _I64, _I32, _P, _F,
+                                           _P]),
+    "dgc_compress_begin_clip": (ctypes.c_int, [_P, _P, _P, _F, _I32, _I64, _I64, ctypes.POINTER(SelectParams), _P,
+                                               _I32, _P, _F, _P, _SZ, _P]),
+    "dgc_batch_compress_begin_clip": (ctypes.c_int, [ctypes.POINTER(BatchDesc), _P, _P, _P, ctypes.POINTER(_I64),
+                                                     _I32, _P, _F, _P, _SZ, _P]),
+    "dgc_batch_compress_begin_ptrs_clip": (ctypes.c_int, [ctypes.POINTER(BatchDesc), ctypes.POINTER(_P), _P, _P,
+                                                          ctypes.POINTER(_I64), _I32, _P, _F, _P, _SZ, _P]),
+    "dgc_compensate_multi_clip": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.POINTER(_I64), ctypes.POINTER(_I64), _I32,
+                                                 _I32, _P, _P, _F, _I32, _I32, _P, _F, _P]),
     "dgc_sgd_step": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(_P),
                                     ctypes.POINTER(_I64), ctypes.POINTER(_I32), _I32, _F, _F, _F, _F, _I32, _P]),
     "dgc_sgd_step16": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(_P),

@@ -54,13 +54,21 @@ class DGCBatch:
                  sample_ratio=0.01, compress_upper_bound=1.3, compress_lower_bound=0.8, max_adaptation_iters=10,
                  resample=True, fp16_values=False, int32_indices=False, device=None, world_size=None, seed=None,
                  deferred_masking=True, fill="auto", dtype=torch.float32, exchange_parts="auto",
-                 resample_order="index", payload_extra=0):
+                 resample_order="index", payload_extra=0, clip=None):
         if fill not in ("auto", "inline", "sparse"):
             raise ValueError(f"fill must be 'auto', 'inline' or 'sparse', not {fill!r}")
         if dtype not in (torch.float32,) + _lib.HALF:
             raise NotImplementedError(f"DGCBatch: fp32, bf16 or fp16 parameters (got {dtype})")
         self.dtype = dtype
         self.half = dtype in _lib.HALF
+        # local gradient clipping fused into K1: a dgc.clip_grad.ClipSpec (norm-2, norm-inf
+        # or value; fp32) — one statistic per tensor over K1's own pointer table, the
+        # coefficients, then the clipped K1: three more launches per step up to 64 tensors
+        if clip is not None and (self.half or not getattr(clip, "batchable", False)):
+            raise NotImplementedError(f"DGCBatch: clip takes a local dgc.clip_grad spec (norm-2, norm-inf or value) "
+                                      f"on fp32 parameters (got {clip!r} on {dtype})")
+        self.clip = clip
+        self.clip_coefs = None   # device float[T] of the last step (None: a fixed clamp)
         if fill == "auto" or self.half:   # the dense zero_() is always right; the re-zero is opt-in (fp32)
             fill = "inline"
         self.fill = fill
@@ -260,7 +268,18 @@ class DGCBatch:
                                           self.momentum, int(self.nesterov), 1, _lib.VD[self.dtype], st),
                        "dgc_compensate16")
             return
-        if grad_ptrs is None:
+        if self.clip is not None:
+            T = len(self.names)
+            if grad_ptrs is None:
+                base = self.grad_flat.data_ptr()
+                grad_ptrs = (ctypes.c_void_p * T)(*[base + 4 * o for o in self.offsets])
+            self.clip_coefs = self.clip.table_coefs(grad_ptrs, self._arrays[0], T, self.device)
+            _lib.check(L.dgc_batch_compress_begin_ptrs_clip(ctypes.byref(self.desc), grad_ptrs,
+                                                            self._mmt_flat.data_ptr(), self._vec_flat.data_ptr(), arr,
+                                                            self.clip.kind, _lib.ptr(self.clip_coefs), self.clip.param,
+                                                            self.ws.data_ptr(), self.ws.numel(), st),
+                       "dgc_batch_compress_begin_ptrs_clip")
+        elif grad_ptrs is None:
             _lib.check(L.dgc_batch_compress_begin(ctypes.byref(self.desc), self.grad_flat.data_ptr(),
                                                   self._mmt_flat.data_ptr(), self._vec_flat.data_ptr(), arr,
                                                   self.ws.data_ptr(), self.ws.numel(), st), "dgc_batch_compress_begin")

@@ -314,7 +314,9 @@ class DGCCompressor:
                 values, indices = self._views(payload, lay, idx.numel())
             elif isinstance(mem, DGCSGDMemory) and self.strided_sample:
                 # fused path: K1 (+sample) -> K3 -> K4 (+update) in one library call
-                grad = mem._clip(tensor).reshape(-1)
+                # a dgc.clip_grad function: stats -> coefs, then the clip in K1's registers
+                fused_clip = mem.fused_clip(tensor.reshape(-1)) if tensor.is_contiguous() else None
+                grad = (tensor if fused_clip is not None else mem._clip(tensor)).reshape(-1)
                 _lib.require_cuda_f32(grad, "DGCCompressor.compress")
                 mem._sync()
                 mmt, vec = mem.state_of(name, grad, True, "DGCCompressor.compress")
@@ -329,10 +331,22 @@ class DGCCompressor:
                 info = torch.empty(_lib.INFO_BYTES, dtype=torch.uint8, device=dev)
                 base = payload.data_ptr()
                 voff, ioff = lay[4], lay[5]
-                _lib.check(L.dgc_compress(_lib.ptr(grad), _lib.ptr(mmt), _lib.ptr(vec), float(mem.momentum),
-                                          int(bool(mem.nesterov)), start, stride, ks, params, _lib.ptr(spec),
-                                          _lib.SPEC_MARGIN, base + voff, base + ioff, base, _lib.ptr(info),
-                                          _lib.ptr(ws), wsz, _lib.SYNC_HOST, _lib.stream_of(dev)), "dgc_compress")
+                if fused_clip is None:
+                    _lib.check(L.dgc_compress(_lib.ptr(grad), _lib.ptr(mmt), _lib.ptr(vec), float(mem.momentum),
+                                              int(bool(mem.nesterov)), start, stride, ks, params, _lib.ptr(spec),
+                                              _lib.SPEC_MARGIN, base + voff, base + ioff, base, _lib.ptr(info),
+                                              _lib.ptr(ws), wsz, _lib.SYNC_HOST, _lib.stream_of(dev)), "dgc_compress")
+                else:
+                    kind, coef, value = fused_clip
+                    st = _lib.stream_of(dev)
+                    _lib.check(L.dgc_compress_begin_clip(_lib.ptr(grad), _lib.ptr(mmt), _lib.ptr(vec),
+                                                         float(mem.momentum), int(bool(mem.nesterov)), start, stride,
+                                                         params, _lib.ptr(spec), kind, _lib.ptr(coef), value,
+                                                         _lib.ptr(ws), wsz, st), "dgc_compress_begin_clip")
+                    _lib.check(L.dgc_compress_finish(_lib.ptr(vec), _lib.ptr(mmt), start, stride, ks, params,
+                                                     _lib.ptr(spec), _lib.SPEC_MARGIN, base + voff, base + ioff, base,
+                                                     _lib.ptr(info), _lib.ptr(ws), wsz, _lib.SYNC_HOST, st),
+                               "dgc_compress_finish")
                 n = self._count(info)
                 values, indices = self._views(payload, lay, n)
                 self._last_info = info

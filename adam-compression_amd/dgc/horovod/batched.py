@@ -28,6 +28,14 @@ velocities become views of the batch's flat buffers (``memory.momentums[name]`` 
 ``velocities[name]``); anything that rebinds them (``memory.load_state_dict``,
 ``compressor.initialize``) is detected at the next step and copied back in.
 
+Gradient clipping (``DGCSGDMemory(gradient_clipping=...)``): a local ``dgc.clip_grad``
+function (norm-2, norm-inf, value; fp32 parameters) is fused — per leg one statistics
+pass over the leg's pointer table, the coefficients, and the clipped K1 (``DGCBatch(clip=)``;
+``dgc_compensate_multi_clip`` for the dense tensors, which clips the exchanged Average
+as the reference does, dgc/compression.py:195-198 -> dgc/memory.py:52-53: at W > 1 the
+Average is first formed in a flat buffer by ``dgc_rank_sum``). The global variants and
+opaque callables keep the per-tensor path.
+
 Gradients: whatever ``p.grad`` is at ``step()`` — a fresh tensor from backward after
 the default ``zero_grad(set_to_none=True)``, or the previous step's output view zeroed
 in place and accumulated into (``set_to_none=False``) — is read in place when it is a
@@ -56,6 +64,7 @@ from .. import _lib
 from .. import comm
 from .._lib import glue as _glue
 from ..batch import DGCBatch
+from ..clip_grad import spec_of
 from ..comm import Average
 from ..compression import DGCCompressor
 from ..memory import DGCSGDMemory
@@ -64,11 +73,17 @@ __all__ = ["BatchedStep", "supported", "auto"]
 
 
 def supported(compression):
-    """The batched step covers DGCCompressor + DGCSGDMemory with strided sampling and no
-    gradient clipping (everything else keeps the per-tensor path)."""
+    """The batched step covers DGCCompressor + DGCSGDMemory with strided sampling and
+    either no gradient clipping or a local ``dgc.clip_grad`` function (norm-2, norm-inf or
+    value, bare or a ``functools.partial``); a global variant or any other callable keeps
+    the per-tensor path, as does everything else."""
     mem = getattr(compression, "memory", None)
-    return (isinstance(compression, DGCCompressor) and isinstance(mem, DGCSGDMemory)
-            and compression.strided_sample and mem.gradient_clipping is None)
+    if not (isinstance(compression, DGCCompressor) and isinstance(mem, DGCSGDMemory) and compression.strided_sample):
+        return False
+    if mem.gradient_clipping is None:
+        return True
+    spec = spec_of(mem.gradient_clipping)
+    return spec is not None and spec.batchable
 
 
 def auto(compression, named_parameters, op):
@@ -86,6 +101,8 @@ def auto(compression, named_parameters, op):
             return False
     params = [p for _, p in named_parameters if p.requires_grad]
     dts = {p.dtype for p in params}
+    if compression.memory.gradient_clipping is not None and dts != {torch.float32}:
+        return False   # the fused clip is fp32; 16-bit parameters call the function per tensor
     return (bool(params) and all(p.is_cuda for p in params) and len(dts) == 1
             and dts <= {torch.float32, torch.bfloat16, torch.float16})
 
@@ -115,6 +132,10 @@ class BatchedStep:
         self.dtype = self.named[0][1].dtype if self.named else torch.float32
         self.half = self.dtype in _lib.HALF
         self._plan = None
+        self.clip = spec_of(self.mem.gradient_clipping) if self.mem.gradient_clipping is not None else None
+        if self.mem.gradient_clipping is not None and (self.clip is None or self.half):
+            raise NotImplementedError("DistributedOptimizer(batch=True): gradient clipping is fused for a local "
+                                      "dgc.clip_grad function on fp32 parameters; anything else runs with batch=False")
         self.mem._before_read.append(self.flush)
         _lib.glue()   # the host glue must be there (fails loudly, like the library)
 
@@ -152,7 +173,7 @@ class BatchedStep:
                          max_adaptation_iters=c.max_adaptation_iters, resample=c.resample,
                          fp16_values=c.fp16_values, int32_indices=c.int32_indices, device=dev,
                          world_size=comm.size(), deferred_masking=True, fill=self.fill, dtype=self.dtype,
-                         payload_extra=dense_bytes)
+                         payload_extra=dense_bytes, clip=self.clip)
             for i, n in enumerate(comp_names):
                 numel, _, k, S, ks, stride = c.attributes[n]
                 if (k, S, ks, stride) != tuple(b.attrs[i]):
@@ -196,6 +217,13 @@ class BatchedStep:
                     # wire values go in an allgather of their own, summed the same way
                     plan["dense_wire"] = torch.empty(dense_bytes, dtype=torch.uint8, device=dev)
                     plan["dense_gathered"] = torch.empty(comm.size() * dense_bytes, dtype=torch.uint8, device=dev)
+            if dense_bytes and self.clip is not None:
+                # the clip takes the exchanged Average: formed in a flat buffer first
+                # (dgc_rank_sum, widened for an fp16 wire), then statistics and K1 over it
+                plan["dense_avg"] = torch.zeros(end, dtype=wire_dt, device=dev)
+                avg32 = plan["dense_avg32"] = (plan["dense_avg"] if wire_dt == torch.float32
+                                               else torch.zeros(end, dtype=torch.float32, device=dev))
+                plan["dense_avg_ptrs"] = (ctypes.c_void_p * T)(*[avg32.data_ptr() + 4 * o for o in offs])
             if self.half:   # the gathered 16-bit gradients (K1-16's dense branch reads one buffer)
                 plan["dense_in"] = torch.zeros(end, dtype=self.dtype, device=dev)
             plan["zeros"] = torch.zeros(max((p.numel() for _, p in dense), default=1), dtype=self.dtype,
@@ -310,19 +338,43 @@ class BatchedStep:
                     src, stride = comm.synchronize(dense_handle).data_ptr(), plan["dense_wire"].numel()
                 else:
                     src, stride = b.gathered.data_ptr() + b.extra_off, b.rank_stride
-                _lib.check(L.dgc_compensate_ranks(ctypes.c_void_p(src), _lib.VD[plan["wire_dtype"]], comm.size(),
-                                                  stride, _lib.ptr(mmt), _lib.ptr(out), plan["dense_numel"],
-                                                  float(mem.momentum), int(bool(mem.nesterov)), st),
-                           "dgc_compensate_ranks")
+                if self.clip is None:
+                    _lib.check(L.dgc_compensate_ranks(ctypes.c_void_p(src), _lib.VD[plan["wire_dtype"]], comm.size(),
+                                                      stride, _lib.ptr(mmt), _lib.ptr(out), plan["dense_numel"],
+                                                      float(mem.momentum), int(bool(mem.nesterov)), st),
+                               "dgc_compensate_ranks")
+                else:
+                    avg, avg32 = plan["dense_avg"], plan["dense_avg32"]
+                    wd = _lib.VD[plan["wire_dtype"]]
+                    _lib.check(L.dgc_rank_sum(ctypes.c_void_p(src), wd, comm.size(), stride, plan["dense_numel"], 1,
+                                              _lib.ptr(avg), st), "dgc_rank_sum")
+                    if avg32 is not avg:   # decompress: tensor.type(vdtype) (dgc/compression.py:196-197)
+                        _lib.check(L.dgc_widen16(_lib.ptr(avg), _lib.ptr(avg32), plan["dense_numel"], wd, st),
+                                   "dgc_widen16")
+                    self._dense_clipped(plan, plan["dense_avg_ptrs"], torch.float32, L, st)
             else:   # one rank: the allreduce is the identity, the fp16 wire a rounding
                 rnd = torch.float16 if self.comp.fp16_values else torch.float32
-                _lib.check(L.dgc_compensate_multi(plan["dense_ptrs"], plan["dense_numels"], plan["dense_offs"],
-                                                  len(plan["dense"]), _lib.VD[rnd], _lib.ptr(mmt), _lib.ptr(out),
-                                                  float(mem.momentum), int(bool(mem.nesterov)), st),
-                           "dgc_compensate_multi")
+                if self.clip is None:
+                    _lib.check(L.dgc_compensate_multi(plan["dense_ptrs"], plan["dense_numels"], plan["dense_offs"],
+                                                      len(plan["dense"]), _lib.VD[rnd], _lib.ptr(mmt), _lib.ptr(out),
+                                                      float(mem.momentum), int(bool(mem.nesterov)), st),
+                               "dgc_compensate_multi")
+                else:
+                    self._dense_clipped(plan, plan["dense_ptrs"], rnd, L, st)
             # p.grad.set_(compensate(accumulate=False)) (dgc/compression.py:195-198)
             glue.bind_grads(plan["dense_params"], plan["dense_views"])
             plan.pop("keep", None)
+
+    def _dense_clipped(self, plan, ptrs, round_to, L, st):
+        """compensate(accumulate=False) of the dense tensors at ``ptrs`` with the clip fused:
+        their statistics (of the values K1 sees: ``round_to``), the coefficients, K1."""
+        mem, T = self.mem, len(plan["dense"])
+        coefs = self.clip.table_coefs(ptrs, plan["dense_numels"], T, plan["dev"], round_to)
+        plan["dense_clip_coefs"] = coefs
+        _lib.check(L.dgc_compensate_multi_clip(ptrs, plan["dense_numels"], plan["dense_offs"], T, _lib.VD[round_to],
+                                               _lib.ptr(plan["dense_mmt"]), _lib.ptr(plan["dense_out"]),
+                                               float(mem.momentum), int(bool(mem.nesterov)), self.clip.kind,
+                                               _lib.ptr(coefs), self.clip.param, st), "dgc_compensate_multi_clip")
 
     def _dense16_exchange(self, plan, L, st):
         """16-bit dense tensors: the gradients gathered into one buffer (2-B copies),

@@ -77,7 +77,7 @@ class _DistributedOptimizer(torch.optim.Optimizer):
             from dgc.horovod import batched
             if not batched.supported(compression):
                 raise ValueError("batch=True needs a DGCCompressor driving a DGCSGDMemory with strided sampling "
-                                 "and no gradient clipping")
+                                 "and no gradient clipping other than a local dgc.clip_grad function")
             self._batched = batched.BatchedStep(compression, named_parameters,
                                                 fill="sparse" if batch == "sparse" else "inline")
         if comm.size() > 1 or os.environ.get("HOROVOD_ELASTIC") == "1":

@@ -7,7 +7,12 @@ The arithmetic runs in ``libdgc_hip.so`` on the MI355X:
 * ``compensate``  -> ``dgc_compensate`` (K1: one fused streaming pass, fp32 with the
   reference's two separate roundings, no FMA contraction);
 * ``update``      -> ``dgc_mask_indices`` (the same masking that ``dgc_compress``
-  fuses into its emit kernel when the compressor drives this memory).
+  fuses into its emit kernel when the compressor drives this memory);
+* ``gradient_clipping`` -> when it is one of ``dgc.clip_grad``'s functions (or a
+  ``functools.partial`` of one) and the gradient is fp32: ``dgc_grad_stats`` ->
+  ``dgc_clip_coefs`` -> ``dgc_compensate_clip``, the clip applied in registers as K1
+  loads the gradient (the input gradient stays as it was). Any other callable is called
+  as the reference calls it, before K1.
 
 ``momentums`` / ``velocities`` stay plain param-shaped tensors of the parameter's dtype
 keyed by name, so ``state_dict`` / ``load_state_dict`` and checkpoints are unchanged.
@@ -19,6 +24,7 @@ import ctypes
 import torch
 
 from . import _lib
+from . import clip_grad
 from . import comm
 
 __all__ = ["Memory", "DGCSGDMemory"]
@@ -62,6 +68,8 @@ class DGCSGDMemory(Memory):
         # callables run before the state is read or replaced: a batched step
         # (dgc/horovod/batched.py) applies a deferred momentum masking there
         self._before_read = []
+        self._clip_spec = (None, None)   # (callable, its dgc.clip_grad.ClipSpec or None)
+        self.last_clip_coef = None       # device float[1] of the last fused clip (None: a fixed clamp)
 
     def _sync(self):
         for fn in self._before_read:
@@ -89,6 +97,27 @@ class DGCSGDMemory(Memory):
     def _clip(self, grad):
         return self.gradient_clipping(grad) if self.gradient_clipping is not None else grad
 
+    def clip_spec(self):
+        """The ``ClipSpec`` of ``gradient_clipping`` when it is a ``dgc.clip_grad`` function
+        (None: no clipping, or an opaque callable)."""
+        fn = self.gradient_clipping
+        if fn is None:
+            return None
+        if self._clip_spec[0] is not fn:
+            self._clip_spec = (fn, clip_grad.spec_of(fn))
+        return self._clip_spec[1]
+
+    def fused_clip(self, grad):
+        """(clip kind, device coefficient or None, clamp value) for K1 when the clip of
+        ``grad`` (contiguous) can be fused: a recognised spec on an fp32 device tensor. The
+        statistic and the coefficient are issued here, stream-ordered; None otherwise."""
+        spec = self.clip_spec()
+        if spec is None or not (torch.is_tensor(grad) and grad.is_cuda and grad.dtype == torch.float32):
+            return None
+        _lib.require_cuda_f32(grad, "DGCSGDMemory.gradient_clipping")
+        coef = self.last_clip_coef = spec.coef(grad)
+        return spec.kind, coef, spec.param
+
     def state_of(self, name, like, accumulate=True, what="DGCSGDMemory.compensate"):
         """(momentum, velocity or None) of ``name``, checked before their pointers reach a
         kernel: contiguous tensors of ``like``'s dtype, device and size. ``load_state_dict``
@@ -115,7 +144,10 @@ class DGCSGDMemory(Memory):
         accumulate=True returns ``velocities[name]`` itself (updated in place);
         accumulate=False (dense tensors) returns a new tensor."""
         self._sync()
-        grad = self._clip(grad)
+        fusable = (self.clip_spec() is not None and torch.is_tensor(grad) and grad.is_cuda
+                   and grad.dtype == torch.float32)
+        if not fusable:
+            grad = self._clip(grad)
         g = grad.contiguous()
         dt = _lib.require_cuda_float(g, "DGCSGDMemory.compensate")
         mmt, _ = self.state_of(name, g, accumulate)
@@ -123,17 +155,16 @@ class DGCSGDMemory(Memory):
         stream = _lib.stream_of(g.device)
         if dt in _lib.HALF:
             return self._compensate16(g, name, accumulate)
-        if accumulate:
-            vec = self.velocities[name]
-            _lib.check(L.dgc_compensate(_lib.ptr(g), _lib.ptr(mmt), _lib.ptr(vec), None, mmt.numel(),
-                                        float(self.momentum), int(bool(self.nesterov)), 1, None, 0, 1, 0,
-                                        stream), "dgc_compensate")
-            return vec
-        out = torch.empty_like(mmt)
-        _lib.check(L.dgc_compensate(_lib.ptr(g), _lib.ptr(mmt), None, _lib.ptr(out), mmt.numel(),
-                                    float(self.momentum), int(bool(self.nesterov)), 0, None, 0, 1, 0,
-                                    stream), "dgc_compensate")
-        return out
+        vec = self.velocities[name] if accumulate else None
+        out = None if accumulate else torch.empty_like(mmt)
+        args = (_lib.ptr(g), _lib.ptr(mmt), _lib.ptr(vec), _lib.ptr(out), mmt.numel(), float(self.momentum),
+                int(bool(self.nesterov)), int(accumulate), None, 0, 1, 0)
+        if fusable:
+            kind, coef, value = self.fused_clip(g)
+            _lib.check(L.dgc_compensate_clip(*args, kind, _lib.ptr(coef), value, stream), "dgc_compensate_clip")
+        else:
+            _lib.check(L.dgc_compensate(*args, stream), "dgc_compensate")
+        return vec if accumulate else out
 
     def _compensate16(self, g, name, accumulate, vec32=None):
         """compensate on a bf16 / fp16 state (K1-16); vec32: optional fp32 image of the

@@ -554,6 +554,74 @@ int dgc_decompress_packed16(const void* payload, int32_t world, int64_t rank_str
 int dgc_gather16(const void* const* srcs, const int64_t* numels, const int64_t* offsets, int32_t count, void* dst,
                  void* stream);
 
+/* ---- K0: local gradient clipping (dgc/clip_grad.py:10-42, run by DGCSGDMemory.compensate
+ * as `gradient_clipping`, dgc/memory.py:52-53) ----
+ * Three stream-ordered steps, none of which reads anything back: a statistic per tensor
+ * (dgc_grad_stats), a coefficient per tensor (dgc_clip_coefs), and the clipping itself —
+ * fused into K1's load of the gradient (the *_clip forms below, which leave the input
+ * gradient as it was) or in place (dgc_clip_apply, the module functions). */
+enum dgc_stat_kind {
+    DGC_STAT_SUMSQ = 0,       /* fl32(sum of g^2): torch.sum(grad.square()) of the global variants */
+    DGC_STAT_NORM2 = 1,       /* fl32(sqrt(sum of g^2)), the root taken of the fp64 sum:           */
+                              /*   grad.norm(2)                                                   */
+    DGC_STAT_ABSMAX = 2       /* max |g|, NaN if any element is: grad.abs().max()                 */
+};
+enum dgc_clip_mode {
+    DGC_COEF_NORM = 0,        /* stat is the norm (NORM2 / ABSMAX / a torch norm):                */
+                              /*   c = fl32(max_norm) * fl32(1 / (stat + 1e-6f))                  */
+    DGC_COEF_GLOBAL_VALUE = 1,/* stat is the averaged SUMSQ: c = sqrtf(stat), a clamp bound       */
+    DGC_COEF_GLOBAL_NORM2 = 2 /* stat is the averaged SUMSQ: NORM with the norm sqrtf(stat)       */
+};
+enum dgc_clip_kind {
+    DGC_CLIP_NONE = 0,
+    DGC_CLIP_SCALE = 1,       /* g = c < 1 ? g * c : g  (one rounding; a NaN c leaves g alone)    */
+    DGC_CLIP_CLAMP = 2        /* g = min(max(g, -c), c) (a NaN g stays NaN, a NaN c gives NaN)    */
+};
+/* dgc_grad_stats: stats[t] = the statistic of srcs[t][0..numels[t]) for `count` tensors
+ *   (srcs, numels: HOST arrays; srcs[t] device floats of any alignment; numel 0 gives 0).
+ *   round_to = DGC_F16 takes each value rounded to fp16 and back first (what K1 sees of a
+ *   one-rank fp16 wire, as dgc_compensate_multi's round_to). The squares and their sum
+ *   are fp64, rounded to fp32 once at the end. The sum's order is fixed by the tensor's
+ *   numel alone — 4096-element workgroup partials in the workspace (each a fixed tree over
+ *   fixed per-lane runs), then one workgroup per tensor that adds them in a fixed order —
+ *   so a tensor's statistic is the same bits alone, in any table, at any alignment. No
+ *   floating-point atomics, no workgroup waits for another: two launches per 64 tensors.
+ * dgc_clip_coefs: clip[t] from stats[t] for a dgc_clip_mode, in the fp32 operations of the
+ *   reference's 0-dim tensor arithmetic (`max_norm / (total_norm + 1e-6)` is torch's
+ *   reciprocal().mul(max_norm): two roundings); no contraction. max_norm is unused by
+ *   DGC_COEF_GLOBAL_VALUE. stats and clip may be the same array.
+ * dgc_clip_apply: tensors[t][i] = clip(tensors[t][i]) in place, with clip[t] (or, clip =
+ *   NULL, clip_value for every tensor: clip_grad_value_'s fixed bound).
+ * The *_clip forms of K1 are the calls they are named after with the gradient clipped as
+ *   it is loaded (after round_to's rounding in dgc_compensate_multi_clip: the exchanged
+ *   Average is what decompress hands compensate): clip points at the coefficient of the
+ *   call's tensor, or at a table with one entry per tensor of the batch / the table; NULL
+ *   with DGC_CLIP_CLAMP uses clip_value. clip_kind DGC_CLIP_NONE is the unclipped call. */
+size_t dgc_grad_stats_workspace(const int64_t* numels, int32_t count);
+int dgc_grad_stats(const float* const* srcs, const int64_t* numels, int32_t count, int32_t kind, int32_t round_to,
+                   float* stats, void* ws, size_t ws_bytes, void* stream);
+int dgc_clip_coefs(const float* stats, int32_t count, int32_t mode, float max_norm, float* clip, void* stream);
+int dgc_clip_apply(float* const* tensors, const int64_t* numels, int32_t count, int32_t clip_kind, const float* clip,
+                   float clip_value, void* stream);
+int dgc_compensate_clip(const float* grad, float* mmt, float* vec, float* out, int64_t n, float momentum,
+                        int32_t nesterov, int32_t accumulate, float* samples, int64_t sample_start,
+                        int64_t sample_stride, int64_t num_samples, int32_t clip_kind, const float* clip,
+                        float clip_value, void* stream);
+int dgc_compress_begin_clip(const float* grad, float* mmt, float* vec, float momentum, int32_t nesterov,
+                            int64_t sample_start, int64_t sample_stride, const dgc_select_params* params,
+                            const float* spec_threshold, int32_t clip_kind, const float* clip, float clip_value,
+                            void* ws, size_t ws_bytes, void* stream);
+int dgc_batch_compress_begin_clip(const dgc_batch_desc* batch, const float* grad, float* mmt, float* vec,
+                                  const int64_t* sample_starts, int32_t clip_kind, const float* clip,
+                                  float clip_value, void* ws, size_t ws_bytes, void* stream);
+int dgc_batch_compress_begin_ptrs_clip(const dgc_batch_desc* batch, const float* const* grads, float* mmt,
+                                       float* vec, const int64_t* sample_starts, int32_t clip_kind,
+                                       const float* clip, float clip_value, void* ws, size_t ws_bytes,
+                                       void* stream);
+int dgc_compensate_multi_clip(const float* const* srcs, const int64_t* numels, const int64_t* offsets, int32_t count,
+                              int32_t round_to, float* mmt, float* out, float momentum, int32_t nesterov,
+                              int32_t clip_kind, const float* clip, float clip_value, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
