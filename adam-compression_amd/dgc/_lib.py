@@ -69,6 +69,23 @@ def info_dict(i, what):
 INFO_BYTES = ctypes.sizeof(SelectInfo)
 
 
+def read_infos(info, whats):
+    """The first ``len(whats)`` dgc_select_info records of the device buffer ``info`` as
+    ``info_dict``s, read in ONE device-to-host copy (a host synchronisation);
+    ``whats[t]`` names record t in the error a broken resample replay raises."""
+    raw = info.cpu().numpy().tobytes()
+    return [info_dict(SelectInfo.from_buffer_copy(raw[t * INFO_BYTES:(t + 1) * INFO_BYTES]), what)
+            for t, what in enumerate(whats)]
+
+
+def resample_order_flag(order):
+    """dgc_select_params.resample_order: 1 lists an untied resample's set in index order,
+    0 keeps torch.topk's order."""
+    if order not in ("index", "topk"):
+        raise ValueError(f"resample_order must be 'index' or 'topk', not {order!r}")
+    return 1 if order == "index" else 0
+
+
 # every sink's pinned words stay allocated for the life of the process: the library
 # holds their addresses (dgc_select_params.status_sink, dgc_decompress_bind_sink)
 _SINK_WORDS = []
@@ -324,6 +341,14 @@ def check(status, what="dgc"):
     if status != DGC_OK:
         msg = lib().dgc_last_error().decode(errors="replace")
         raise RuntimeError(f"{what} failed (status {status}): {msg}")
+
+
+def payload_layout(capacity, vdtype, idtype):
+    """(rank_stride, values offset, indices offset) in bytes of one rank's packed payload
+    ``[count | values(capacity) | indices(capacity)]`` (dgc_payload_layout)."""
+    voff, ioff = ctypes.c_int64(), ctypes.c_int64()
+    stride = lib().dgc_payload_layout(capacity, VD[vdtype], ID[idtype], ctypes.byref(voff), ctypes.byref(ioff))
+    return stride, voff.value, ioff.value
 
 
 def stream_of(device):

@@ -12,13 +12,11 @@ each tensor at a 1024-element-aligned offset) and runs
     dgc_batch_compress   K1 over all tensors, K3 for all thresholds, the selection
                          chain with per-tensor state, one packed payload
     one allgather        the packed payload, RCCL over xGMI (gloo stages via the host)
-    decompress           dgc_decompress_packed (zero fill + scatter) over the flat output
-                         (``fill="auto"``/``"inline"``, the default), or — opted in with
-                         ``fill="sparse"`` by a caller that owns the output and never writes
-                         it — dgc_decompress_packed_over: only the previous step's gathered
-                         indices are re-zeroed, as in ``DGCBucket`` (writes through ``.data``
-                         or raw pointers do not bump torch's version counter, so the
-                         re-zero cannot see them: see dgc/bucket.py)
+    decompress           zero fill + scatter over the flat output (``fill="auto"``/``"inline"``,
+                         the default), or — opted in with ``fill="sparse"`` by a caller that
+                         owns the output and never writes it — only the previous step's
+                         gathered indices are re-zeroed, as in ``DGCBucket``: the receive side
+                         both engines share (``Receiver``, dgc/exchange.py) explains it
 
 with O(1) launches per phase and no host synchronisation. The payload carries flat
 indices (tensor offset + index in the tensor), tensor after tensor.
@@ -34,22 +32,15 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from . import comm
-from .exchange import SplitExchange, split_parts
+from .compression import DGCCompressor
+from .exchange import ReceiveSide, Receiver
 
 __all__ = ["DGCBatch"]
 
 SEG = 1024   # tensors start at multiples of this many elements (the kernels' segment)
 
 
-def _attributes(numel, ratio, sample_ratio):
-    """(num_selects, num_samples, top_k_samples, sample_stride): dgc/compression.py:56-89."""
-    from .compression import DGCCompressor
-    stride, samples = DGCCompressor._stride_and_samples(numel, ratio, sample_ratio)
-    return int(math.ceil(numel * ratio)), samples, int(math.ceil(samples * ratio)), stride
-
-
-class DGCBatch:
+class DGCBatch(ReceiveSide):
     def __init__(self, named_shapes, compress_ratio=0.001, momentum=0.9, nesterov=False, momentum_masking=True,
                  sample_ratio=0.01, compress_upper_bound=1.3, compress_lower_bound=0.8, max_adaptation_iters=10,
                  resample=True, fp16_values=False, int32_indices=False, device=None, world_size=None, seed=None,
@@ -69,12 +60,9 @@ class DGCBatch:
                                       f"on fp32 parameters (got {clip!r} on {dtype})")
         self.clip = clip
         self.clip_coefs = None   # device float[T] of the last step (None: a fixed clamp)
-        if fill == "auto" or self.half:   # the dense zero_() is always right; the re-zero is opt-in (fp32)
-            fill = "inline"
-        self.fill = fill
+        self._fill = fill
         self.exchange_parts = exchange_parts
-        if resample_order not in ("index", "topk"):
-            raise ValueError(f"resample_order must be 'index' or 'topk', not {resample_order!r}")
+        _lib.resample_order_flag(resample_order)   # validates
         # "index": a resampled tensor whose k-th largest candidate is untied lists its
         # top-k set in index order (the decompress and the memory update depend on the
         # set only; dgc_select_params.resample_order); "topk": torch.topk's order always
@@ -88,7 +76,7 @@ class DGCBatch:
         self.shapes = {n: tuple(s) for n, s in named_shapes}
         self.numels = [math.prod(self.shapes[n]) for n in self.names]
         self.momentum, self.nesterov, self.momentum_masking = float(momentum), bool(nesterov), bool(momentum_masking)
-        self.sample_ratio = min(max(sample_ratio, 0.01), 1.0)
+        _, self.sample_ratio = DGCCompressor._normalized(compress_ratio, sample_ratio)
         self.upper, self.lower = float(compress_upper_bound), float(compress_lower_bound)
         self.max_iters, self.resample = int(max_adaptation_iters), bool(resample)
         self.vdtype = torch.float16 if fp16_values else dtype
@@ -124,11 +112,11 @@ class DGCBatch:
         """(Re-)derive every tensor's attributes for a compress ratio and write the
         device tables — ``DGCCompressor.initialize`` (dgc/compression.py:56-89), also
         what ``warmup_compress_ratio`` re-runs on a ratio change (:91-107)."""
-        ratio = compress_ratio if compress_ratio <= 1.0 else 1.0 / compress_ratio
+        ratio, _ = DGCCompressor._normalized(compress_ratio, self.sample_ratio)
         self.flush()   # a pending masking lives in the old workspace
         self.ratio = ratio
         T = len(self.names)
-        self.attrs = [_attributes(n, ratio, self.sample_ratio) for n in self.numels]
+        self.attrs = [DGCCompressor._attributes(n, ratio, self.sample_ratio) for n in self.numels]
         arr = lambda xs: (ctypes.c_int64 * T)(*xs)   # noqa: E731
         self._arrays = [arr(self.numels), arr(self.offsets), arr([a[0] for a in self.attrs]),
                         arr([a[1] for a in self.attrs]), arr([a[2] for a in self.attrs]), arr([a[3] for a in self.attrs])]
@@ -143,7 +131,7 @@ class DGCBatch:
         d.deferred_masking = int(self.deferred_masking)
         d.dtype = _lib.VD[self.dtype]
         d.status_sink = self.status.address
-        d.resample_order = 1 if self.resample_order == "index" else 0
+        d.resample_order = _lib.resample_order_flag(self.resample_order)
         self.desc = d
         L = self._L
         wsz = L.dgc_batch_workspace(ctypes.byref(d))
@@ -153,45 +141,11 @@ class DGCBatch:
         _lib.check(L.dgc_batch_init(ctypes.byref(d), self.ws.data_ptr(), wsz, _lib.stream_of(self.device)),
                    "dgc_batch_init")
         self.capacity = sum(a[0] for a in self.attrs)
-        from .compression import _layout
-        self.rank_stride, self.voff, self.ioff = _layout(self.capacity, self.vdtype, self.idtype)
-        # W > 1, fp32: the allgather in parts, each scattered as it lands (dgc/exchange.py)
-        # (W = 1 exchanges too when comm.one_rank_collectives(): the RCCL tests' one-rank group)
-        self.exchanging = self.world > 1 or comm.one_rank_collectives()
-        self.parts = 1 if self.half else split_parts(self.world, self.capacity, self.exchange_parts)
-        self.extra_off = None
-        if self.payload_extra > 0 and self.parts == 1:
-            self.extra_off = self.rank_stride
-            self.rank_stride = -(-(self.rank_stride + self.payload_extra) // 256) * 256
-        # fill="sparse": two payload / gather buffers, so the previous step's gathered
-        # indices stay readable for the re-zero; a new layout forgets them
-        nbuf = 2 if self.fill == "sparse" else 1
-        self._payloads = [torch.zeros(self.rank_stride, dtype=torch.uint8, device=self.device) for _ in range(nbuf)]
-        self.xchg = None
-        self._inflight = None
-        if self.parts > 1:
-            self.xchg = SplitExchange(self.capacity, self.flat_numel, self.world, self.parts, self.vdtype,
-                                      self.idtype, self.device, nbuf)
-            self._gathers = self.xchg.gathers
-        else:
-            self._gathers = ([torch.zeros(self.world * self.rank_stride, dtype=torch.uint8, device=self.device)
-                              for _ in range(nbuf)] if self.exchanging else self._payloads)
-        self._par = 0
-        self._last_out = None
-        self._last_gathered = None
-        self.dec_ws = (torch.empty(L.dgc_decompress_packed_workspace(self.flat_numel, self.world, self.capacity),
-                                   dtype=torch.uint8, device=self.device) if self.xchg is None else None)
-        self.status.bind(self.dec_ws if self.xchg is None else self.xchg.ws)
-
-    @property
-    def payload(self):
-        """This rank's packed payload of the current step."""
-        return self._payloads[self._par % len(self._payloads)]
-
-    @property
-    def gathered(self):
-        """The allgather buffer of the current step (the payload itself at W = 1)."""
-        return self._gathers[self._par % len(self._gathers)]
+        # a new layout: a new receive side (payload / gather buffers, exchange, decompress
+        # workspace bound to ``status``), which remembers nothing of the previous step
+        self.rx = Receiver(self.capacity, self.flat_numel, self.world, self.vdtype, self.idtype, self.device,
+                           self.status, self._fill, self.exchange_parts, self.payload_extra, self.half,
+                           unsent="DGCBatch: decompress of a split exchange before send() / exchange()")
 
     def flush(self):
         """Applies a deferred masking now (no-op when none is pending)."""
@@ -254,7 +208,7 @@ class DGCBatch:
         self.status.check()
         starts = self.draw_starts() if starts is None else starts
         self.starts = starts
-        self._par += 1   # a step starts: the other payload / gather buffer
+        self.rx.begin()
         arr = (ctypes.c_int64 * len(starts))(*starts)
         self._starts_arr = arr
         L, st = self._L, _lib.stream_of(self.device)
@@ -317,75 +271,29 @@ class DGCBatch:
         """Issues the exchange of this step's payload (W > 1): one allgather, or one per
         part (split); ``decompress`` waits for it. Nothing is issued in between, so a
         single allgather goes out on the current stream (``comm.COLLECTIVE_ISSUE``)."""
-        if self.exchanging:
-            if self.xchg is not None:
-                self._inflight = self.xchg.send(self.payload, self.gathered)
-            else:
-                self._inflight = [comm.allgather_packed_async(self.payload, out=self.gathered, wait=True)]
-
-    def exchange(self):
-        """The exchange; a single allgather is also waited for here, a split one part by
-        part in ``decompress``."""
-        self.send()
-        if self.xchg is None and self._inflight:
-            self._inflight.pop().wait()
-            self._inflight = None
+        self.rx.send()
 
     def decompress(self, out_flat=None):
         """out = the rank-order sum of the gathered entries / W, +0.0 elsewhere (every tensor).
 
         fill="sparse": when ``out`` still holds exactly the previous decompress's result
-        (same storage, torch version counter unchanged — our writes are raw-pointer
-        writes) and is not the gradient buffer (the batched optimizer decompresses into
-        p.grad, rewritten by every backward), the zero_() re-zeroes only the previous
-        step's gathered indices (dgc_decompress_packed_over) instead of the whole
-        buffer: identical result, W * capacity slots instead of flat_numel."""
+        and is not the gradient buffer (the batched optimizer decompresses into p.grad,
+        rewritten by every backward), only the previous step's gathered indices are
+        re-zeroed instead of the whole buffer (``Receiver``, dgc/exchange.py)."""
         out = self.out_flat if out_flat is None else out_flat
         if _lib.require_cuda_float(out, "DGCBatch.decompress") != self.dtype or out.numel() != self.flat_numel \
                 or out.device != self.device:
             raise ValueError(f"DGCBatch.decompress: out_flat must be a contiguous {self.dtype} tensor of "
                              f"{self.flat_numel} elements on {self.device} (got {out.dtype} [{out.numel()}] on "
                              f"{out.device})")
-        L = self._L
-        st = _lib.stream_of(self.device)
-        cur = self.gathered
-        handles, self._inflight = self._inflight or [], None
-        if self.xchg is None:
-            for h in handles:
-                h.wait()
-        elif self.exchanging and not handles:
-            raise RuntimeError("DGCBatch: decompress of a split exchange before send() / exchange()")
         if self.half:   # zero_(), the runs in rank order (each add rounded), the 1/W scale
-            _lib.check(L.dgc_decompress_packed16(cur.data_ptr(), self.world, self.rank_stride, self.capacity,
-                                                 _lib.VD[self.vdtype], _lib.ID[self.idtype], out.data_ptr(),
-                                                 _lib.VD[self.dtype], self.flat_numel, 1.0 / self.world,
-                                                 ctypes.c_void_p(self.status.decompress_words), st),
-                       "dgc_decompress_packed16")
-            return out
-        aliased = out.untyped_storage().data_ptr() == self.grad_flat.untyped_storage().data_ptr()
-        reusable = (self.fill == "sparse" and not aliased and self._last_gathered is not None
-                    and self._last_gathered is not cur
-                    and self._last_out == (out.data_ptr(), out.numel(), out._version))
-        if self.xchg is not None:   # zero_() first (it runs under the first part's collective)
-            if reusable:
-                self.xchg.clear(self._last_gathered, out, st)
-            else:
-                _lib.check(L.dgc_fill_zero(out.data_ptr(), self.flat_numel, st), "dgc_fill_zero")
-            self.xchg.scatter(cur, handles, out, 1.0 / self.world, reusable)
+            self.rx.wait()
+            _lib.check(self._L.dgc_decompress_packed16(
+                self.gathered.data_ptr(), self.world, self.rank_stride, self.capacity, _lib.VD[self.vdtype],
+                _lib.ID[self.idtype], out.data_ptr(), _lib.VD[self.dtype], self.flat_numel, 1.0 / self.world,
+                ctypes.c_void_p(self.status.decompress_words), _lib.stream_of(self.device)), "dgc_decompress_packed16")
         else:
-            args = (self.world, self.rank_stride, self.capacity, _lib.VD[self.vdtype], _lib.ID[self.idtype],
-                    out.data_ptr(), self.flat_numel, 1.0 / self.world, self.dec_ws.data_ptr(), self.dec_ws.numel(), st)
-            if reusable:
-                _lib.check(L.dgc_decompress_packed_over(cur.data_ptr(), self._last_gathered.data_ptr(), *args),
-                           "dgc_decompress_packed_over")
-            else:
-                # the zero fill and the scatter in one call: the fill also resets the scatter's status words
-                _lib.check(L.dgc_decompress_packed(cur.data_ptr(), *args), "dgc_decompress_packed")
-        if aliased:
-            self._last_out = self._last_gathered = None
-        else:
-            self._last_out = (out.data_ptr(), out.numel(), out._version)
-            self._last_gathered = cur
+            self.rx.decompress(out, out.untyped_storage().data_ptr() == self.grad_flat.untyped_storage().data_ptr())
         return out
 
     def step(self, starts=None):
@@ -396,12 +304,7 @@ class DGCBatch:
     # ---------------------------------------------------------------- results
     def infos(self):
         self.status.check(sync=True)
-        raw = self.info.cpu().numpy().tobytes()
-        out = []
-        for t in range(len(self.names)):
-            i = _lib.SelectInfo.from_buffer_copy(raw[t * _lib.INFO_BYTES:(t + 1) * _lib.INFO_BYTES])
-            out.append(_lib.info_dict(i, f"DGCBatch tensor {self.names[t]}"))
-        return out
+        return _lib.read_infos(self.info, [f"DGCBatch tensor {n}" for n in self.names])
 
     def transmitted(self, rank_payload=None):
         """{name: (values, indices)} of one rank's payload (this rank's by default), with

@@ -56,14 +56,6 @@ class _PackedHandle:
 _OURS = 0x444743454D495454   # payload header word 1 of a compress-emitted payload ("DGCEMITT")
 
 
-def _layout(capacity, vdtype, idtype):
-    import ctypes
-    voff, ioff = ctypes.c_int64(), ctypes.c_int64()
-    stride = _lib.lib().dgc_payload_layout(capacity, _lib.VD[vdtype], _lib.ID[idtype],
-                                           ctypes.byref(voff), ctypes.byref(ioff))
-    return stride, voff.value, ioff.value
-
-
 class DGCCompressor:
     def __init__(self, compress_ratio, memory=None,
                  sample_ratio=0.01, strided_sample=True,
@@ -75,7 +67,7 @@ class DGCCompressor:
         self.op = Average
         self.fp16_values = fp16_values
         self.int32_indices = int32_indices
-        ratio = compress_ratio if compress_ratio <= 1.0 else 1.0 / compress_ratio
+        ratio, self.sample_ratio = self._normalized(compress_ratio, sample_ratio)
         self.base_compress_ratio = self.compress_ratio = ratio
         self.memory = Memory if memory is None else memory
         self.warmup_epochs = warmup_epochs
@@ -92,7 +84,6 @@ class DGCCompressor:
                 self.warmup_coeff = warmup_coeff
         else:
             self.warmup_coeff = 1
-        self.sample_ratio = min(max(sample_ratio, 0.01), 1.0)
         self.strided_sample = strided_sample
         self.compress_upper_bound = compress_upper_bound
         self.compress_lower_bound = compress_lower_bound
@@ -109,6 +100,12 @@ class DGCCompressor:
 
     # ------------------------------------------------------------------ host math
     @staticmethod
+    def _normalized(compress_ratio, sample_ratio):
+        """(compress_ratio as a fraction, sample_ratio clamped) of dgc/compression.py:29-43."""
+        ratio = compress_ratio if compress_ratio <= 1.0 else 1.0 / compress_ratio
+        return ratio, min(max(sample_ratio, 0.01), 1.0)
+
+    @staticmethod
     def _stride_and_samples(numel, ratio, sample_ratio):
         """(sample_stride, num_samples) of dgc/compression.py:66-83."""
         if sample_ratio >= 1.0:
@@ -123,6 +120,13 @@ class DGCCompressor:
             stride -= 8
         return stride, numel // stride
 
+    @classmethod
+    def _attributes(cls, numel, ratio, sample_ratio):
+        """(num_selects, num_samples, top_k_samples, sample_stride) of one tensor
+        (dgc/compression.py:56-89), ``ratio`` and ``sample_ratio`` as ``_normalized``."""
+        stride, samples = cls._stride_and_samples(numel, ratio, sample_ratio)
+        return int(math.ceil(numel * ratio)), samples, int(math.ceil(samples * ratio)), stride
+
     def initialize(self, named_parameters):
         """Per-tensor (numel, shape, num_selects, num_samples, top_k_samples, sample_stride)
         (dgc/compression.py:56-89)."""
@@ -135,12 +139,11 @@ class DGCCompressor:
             else:
                 assert isinstance(param, (list, tuple))
                 numel, shape = param[0], param[1]
-            stride, samples = self._stride_and_samples(numel, self.compress_ratio, self.sample_ratio)
+            num_selects, samples, top_k_samples, stride = self._attributes(numel, self.compress_ratio,
+                                                                           self.sample_ratio)
             if comm.rank() == 0 and self.sample_ratio < 1.0 and samples == numel and stride == 1 \
                     and numel <= int(math.ceil(2 / self.compress_ratio)):
                 print(f"Warning: {name} with {numel} elements transmits 1 gradient element")
-            top_k_samples = int(math.ceil(samples * self.compress_ratio))
-            num_selects = int(math.ceil(numel * self.compress_ratio))
             self.attributes[name] = (numel, shape, num_selects, samples, top_k_samples, stride)
             self._params = {key: v for key, v in self._params.items() if key[0] != name}
             self._spec.pop(name, None)
@@ -215,7 +218,7 @@ class DGCCompressor:
         k = self.attributes[name][2]
         vdt = torch.float16 if self.fp16_values else dtype
         idt = torch.int32 if self.int32_indices else torch.int64
-        stride, voff, ioff = _layout(k, vdt, idt)
+        stride, voff, ioff = _lib.payload_layout(k, vdt, idt)
         payload = torch.empty(stride, dtype=torch.uint8, device=device)
         return payload, (k, vdt, idt, stride, voff, ioff)
 
@@ -372,13 +375,11 @@ class DGCCompressor:
         """The emitted count, read with the whole selection record in ONE device-to-host
         copy (the one host sync the exact-length [n, 1] outputs need); raises if the
         resample replay reported a broken multi-workgroup phase."""
-        return _lib.info_dict(_lib.SelectInfo.from_buffer_copy(info.cpu().numpy().tobytes()),
-                              "DGCCompressor.compress")["count"]
+        return _lib.read_infos(info, ["DGCCompressor.compress"])[0]["count"]
 
     def last_info(self):
         """Selection record of the last compress (branch, counts, thresholds) — diagnostics."""
-        return _lib.info_dict(_lib.SelectInfo.from_buffer_copy(self._last_info.cpu().numpy().tobytes()),
-                              "DGCCompressor")
+        return _lib.read_infos(self._last_info, ["DGCCompressor"])[0]
 
     def decompress(self, tensor, ctx):
         """dgc/compression.py:179-198. An index outside the gradient (or a gathered

@@ -420,3 +420,39 @@ def test_batch_index_order_wide_span_resample():
     for name in bs[0].names:
         assert torch.equal(bs[0].velocity_of(name).view(torch.int32), bs[1].velocity_of(name).view(torch.int32))
         assert torch.equal(bs[0].momentum_of(name).view(torch.int32), bs[1].momentum_of(name).view(torch.int32))
+
+
+@pytest.mark.parametrize("fill", ["inline", "sparse"])
+def test_bucket_and_batch_agree_through_shared_receive_side(fill):
+    """DGCBucket and a one-tensor DGCBatch with identical settings run the same steps
+    through the shared receive side (dgc/exchange.py): equal header counts, bit-equal
+    payload entries and dense outputs every step, bit-equal momentum and velocity at the
+    end. fill="sparse": an in-place write on the bucket's output after step 1 sends its
+    next decompress to the dense fill, the batch's stays on the sparse re-zero."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from dgc.batch import DGCBatch
+    from dgc.bucket import DGCBucket
+    N = 1_000_000
+    kw = dict(compress_ratio=0.001, momentum=0.9, nesterov=True, seed=9, resample_order="topk", fill=fill,
+              device=DEV)
+    bucket = DGCBucket(N, **kw)
+    batch = DGCBatch([("w", (N,))], **kw)
+    out = torch.zeros(N, device=DEV)
+    scales = [1, 1, 0.1, 3, 1]
+    for s, scale in enumerate(scales):
+        g = torch.from_numpy(synth.gradient(40 + s, N, "normal", scale)).to(DEV)
+        bucket.step(g, out)
+        batch.grad("w").copy_(g)
+        got = batch.step()
+        torch.cuda.synchronize()
+        pa, pb = bucket.payload, batch.payload
+        count = int(pa[:8].view(torch.int64).item())
+        assert count == int(pb[:8].view(torch.int64).item()), s
+        assert torch.equal(pa[bucket.voff: bucket.voff + 4 * count], pb[batch.voff: batch.voff + 4 * count]), s
+        assert torch.equal(pa[bucket.ioff: bucket.ioff + 8 * count], pb[batch.ioff: batch.ioff + 8 * count]), s
+        assert torch.equal(out.view(torch.int32), got[:N].view(torch.int32)), s
+        if fill == "sparse" and s == 1:
+            out[s::97].fill_(7.0)
+    assert torch.equal(bucket.mmt.view(torch.int32), batch.momentum_of("w").view(torch.int32))
+    assert torch.equal(bucket.vec.view(torch.int32), batch.velocity_of("w").view(torch.int32))

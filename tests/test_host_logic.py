@@ -106,3 +106,25 @@ def test_distributed_optimizer_default_picks_batched_only_when_equivalent():
     assert not batched.auto(comp, cpu, Sum)
     assert not batched.auto(quiet(DGCCompressor, 0.01), cpu, Average)   # Memory, not DGCSGDMemory
     assert not batched.auto(quiet(DGCCompressor, 0.01, memory=mem, strided_sample=False), cpu, Average)
+
+
+def test_reuse_guard_on_cpu_tensors():
+    """The receive side's "output still holds last step's result" guard (fill="sparse",
+    dgc/exchange.py) on plain tensors: torch's version counter sees in-place writes; it
+    does not see writes through ``.data`` — the documented blind spot, pinned here so it
+    is not changed silently."""
+    from dgc.exchange import ReuseMemory
+    mem, gathered = ReuseMemory(), torch.zeros(4, dtype=torch.uint8)
+    out, other = torch.zeros(8), torch.zeros(8)
+    assert not mem.reusable(out)
+    mem.remember(out, gathered)
+    assert mem.reusable(out)
+    assert not mem.reusable(other)
+    out.data.add_(1)
+    assert mem.reusable(out)
+    out.add_(1)
+    assert not mem.reusable(out)
+    mem.remember(out, gathered)
+    assert mem.reusable(out)
+    mem.forget()
+    assert not mem.reusable(out) and not mem.reusable(other)

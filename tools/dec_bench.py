@@ -25,7 +25,7 @@ sys.path.insert(0, os.path.join(REPO, "adam-compression_amd"))
 import torch  # noqa: E402
 
 from dgc import _lib  # noqa: E402
-from dgc.compression import _layout  # noqa: E402
+from dgc._lib import payload_layout as _layout  # noqa: E402
 
 
 def timeit(fn, reps):
