@@ -1,6 +1,6 @@
 // K0: local gradient clipping (dgc/clip_grad.py:10-42) — the statistic of every tensor,
 // the coefficient from it, and the in-place clip of the module functions. The fused
-// clip is K1's (compensate.hip, select.hip: clip1 in dgc_common.hpp).
+// clip is K1's (compensate.hip, select_k1.hpp: clip1 in dgc_common.hpp).
 //
 // Statistics: torch's CPU norm sums in an order that depends on its thread count and
 // vector width, so the reference has no fixed answer to reproduce; this one is fixed by

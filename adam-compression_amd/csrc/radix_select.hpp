@@ -49,8 +49,8 @@ struct RSState {
     uint64_t nan_count;
     uint32_t tickets[4];
     uint32_t win_n;                    // > 0: the passes read the K1 sample window list of
-                                       // win_n keys instead of the samples (select.hip)
-    uint32_t small_done;               // select.hip: a window of <= kSmallN keys was selected
+                                       // win_n keys instead of the samples (select_thresholds.hpp)
+    uint32_t small_done;               // select_thresholds.hpp: a window of <= kSmallN keys was selected
                                        // in one workgroup; the passes skip the task
     unsigned long long hist[3][kRsBins];
 };
@@ -432,7 +432,7 @@ __device__ __forceinline__ void rs_small_wg(const float* __restrict__ x, int64_t
     RS_STAMP(9);
 }
 
-// The k-th largest |x| of a K1 sample WINDOW (select.hip: every sample with key >= the
+// The k-th largest |x| of a K1 sample WINDOW (select_k1.hpp: every sample with key >= the
 // window threshold, ks..kWinMax of them) in ONE 1024-thread workgroup, PER keys per
 // thread in registers. The window's keys all sit within a few octaves above its
 // threshold — the few bins of their exponents, where a fixed-digit pass 0 serialises
@@ -527,7 +527,7 @@ __device__ __forceinline__ void rs_window_wg(const float* __restrict__ x, int64_
     __syncthreads();
 }
 
-// K1 also histograms the window as it appends to it (select.hip k_compensate_list): one
+// K1 also histograms the window as it appends to it (select_k1.hpp k_compensate_list): one
 // agent atomic per windowed sample (~3 ks of the S samples) into kWinBins bins of
 // 2^kWinShift key units above the window key — bins 0 .. kWinBins - 3 span a factor
 // of ~1.4 in |x| —, the keys past that range in bin kWinBins - 2 and NaN in the last.

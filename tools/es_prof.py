@@ -1,5 +1,5 @@
 """Where the model sets' merged emit + K5s launch (k_emit_wide_t<true>) spends its time,
-in the bench's steady state: the profiling build's per-workgroup stamps (select.hip
+in the bench's steady state: the profiling build's per-workgroup stamps (select_count.hpp
 ES_STAMP) for the last step — every emit workgroup's entry, scan done and end; every set
 workgroup's entry, its tensor's gather seen complete, and end — against the launch's
 first entry.
@@ -27,7 +27,7 @@ SEG, GROUP_QUARTER, SET_COOP, SET_BIG, SET_GMIN = 1024, 256, 16384, 128, 4
 
 
 def layout(b):
-    """(emit workgroups per tensor, set workgroups per tensor) as select.hip's bt_blocks."""
+    """(emit workgroups per tensor, set workgroups per tensor) as select_layout.hpp's bt_blocks."""
     grp, sets = [], []
     for n, (k, S, ks, stride) in zip(b.numels, b.attrs):
         nseg = -(-n // SEG)

@@ -1,6 +1,6 @@
 """Where a model set's count pass (k_count_pass, the step's last launch of it) and the
 multi-threshold lowering (k_lower_counts) spend their time: the profiling build's
-per-workgroup stamps (select.hip PASS_STAMP) for the last step — entry, past the
+per-workgroup stamps (select_count.hpp PASS_STAMP) for the last step — entry, past the
 tensor gate, loads done, arrival (atomics issued), end.
 
   make -C adam-compression_amd/csrc k5prof
