@@ -339,6 +339,21 @@ __device__ __forceinline__ void st_stream(float4* p, const float4& v, bool wt) {
         st_nt(p, v);
     }
 }
+
+// The same accesses through a global-typed pointer (K1): global_ instructions whatever the
+// compiler can prove about where the pointer came from.
+__device__ __forceinline__ float4 ld_nt(DGC_GLB const float4* p) {
+    const f4v x = __builtin_nontemporal_load(reinterpret_cast<DGC_GLB const f4v*>(p));
+    return make_float4(x[0], x[1], x[2], x[3]);
+}
+
+__device__ __forceinline__ void st_stream(DGC_GLB float4* p, const float4& v, bool wt) {
+    const f4v x = {v.x, v.y, v.z, v.w};
+    if (wt)   // uniform
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(x) : "memory");
+    else
+        __builtin_nontemporal_store(x, reinterpret_cast<DGC_GLB f4v*>(p));
+}
 }  // namespace dgc
 
 namespace dgc {

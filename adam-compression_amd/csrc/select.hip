@@ -556,20 +556,31 @@ static int one_ws(const dgc_select_params* p, int64_t s_start, int64_t s_stride,
 
 // K1 (+ fused strided sample + speculative candidate lists at spec[0]).
 // clip_kind / ca: the gradient clipped as K1 loads it (dgc_compress_begin_clip).
+// lds: bytes of LDS the launch asks for and the kernel never touches, which bounds how many
+// workgroups a CU holds. A one-tensor call (the flat bucket) past the write-through size
+// asks for kK1FlatLds: 3 workgroups then fit a CU's 160 KB, 3 waves per SIMD with 12 KB of
+// loads in flight each. K1's registers allow 6-7 waves, and flat-1B measured slower the more
+// of them were resident (same box, K1 ms: 7 waves 3.44-3.49, 5 waves 3.43, 4 waves
+// 3.24-3.42, 3 waves 3.19-3.41, 2 waves 3.48; DESIGN.md §5 "K1's schedule"). Every other
+// launch — a batch, a bucket of at most kWriteThroughMax elements — keeps the
+// register-limited occupancy: the model sets measured faster with it, and no small flat
+// bucket was measured either way.
+constexpr unsigned kK1FlatLds = 48u << 10;
+
 template <bool NEST, bool ONE, typename... Args>
-static void launch_k1_clip(int32_t clip_kind, dim3 gd, hipStream_t s, Args... args) {
+static void launch_k1_clip(int32_t clip_kind, unsigned lds, dim3 gd, hipStream_t s, Args... args) {
     if (clip_kind == DGC_CLIP_SCALE)
-        hipLaunchKernelGGL((k_compensate_list<NEST, ONE, DGC_CLIP_SCALE>), gd, dim3(kBlock), 0, s, args...);
+        hipLaunchKernelGGL((k_compensate_list<NEST, ONE, DGC_CLIP_SCALE>), gd, dim3(kBlock), lds, s, args...);
     else if (clip_kind == DGC_CLIP_CLAMP)
-        hipLaunchKernelGGL((k_compensate_list<NEST, ONE, DGC_CLIP_CLAMP>), gd, dim3(kBlock), 0, s, args...);
+        hipLaunchKernelGGL((k_compensate_list<NEST, ONE, DGC_CLIP_CLAMP>), gd, dim3(kBlock), lds, s, args...);
     else
-        hipLaunchKernelGGL((k_compensate_list<NEST, ONE, DGC_CLIP_NONE>), gd, dim3(kBlock), 0, s, args...);
+        hipLaunchKernelGGL((k_compensate_list<NEST, ONE, DGC_CLIP_NONE>), gd, dim3(kBlock), lds, s, args...);
 }
 
 template <bool ONE, typename... Args>
-static void launch_k1(bool nesterov, int32_t clip_kind, dim3 gd, hipStream_t s, Args... args) {
-    if (nesterov) launch_k1_clip<true, ONE>(clip_kind, gd, s, args...);
-    else launch_k1_clip<false, ONE>(clip_kind, gd, s, args...);
+static void launch_k1(bool nesterov, int32_t clip_kind, unsigned lds, dim3 gd, hipStream_t s, Args... args) {
+    if (nesterov) launch_k1_clip<true, ONE>(clip_kind, lds, gd, s, args...);
+    else launch_k1_clip<false, ONE>(clip_kind, lds, gd, s, args...);
 }
 
 static int k1_clip_check(int32_t kind, const float* clip, const char* who) {
@@ -608,8 +619,9 @@ int compress_begin(const float* grad, float* mmt, float* vec, float momentum, bo
         StartChunk one{};   // the start (and the tables, ot) in the arguments: no k_put_one
         one.count = 1;
         one.start[0] = ot.start;
-        launch_k1<true>(nesterov, clip_kind, dim3((unsigned)L.grid[BT_K1]), s, grad, mmt, vec, momentum, w, one,
-                        (int)write_through(n), ot, ca);
+        const bool wt = write_through(n);
+        launch_k1<true>(nesterov, clip_kind, wt ? 0u : kK1FlatLds, dim3((unsigned)L.grid[BT_K1]), s, grad, mmt, vec,
+                        momentum, w, one, (int)wt, ot, ca);
         DGC_LAUNCHED();
     } else {
         hipLaunchKernelGGL(k_put_one, dim3(1), dim3(64), 0, s, w, ot);
@@ -810,7 +822,7 @@ int batch_compress_begin(const dgc_batch_desc* b, const float* grad, const float
     if (L.T <= 64) arg = start_chunk(h, starts, grads, 0);
     else DGC_TRY(put_starts(h, starts, grads, w, s));
     if (L.grid[BT_K1] > 0x7FFFFFFFLL) DGC_FAIL(DGC_ERR_INVALID, "dgc_batch_compress: too many segments");
-    launch_k1<false>(b->nesterov != 0, clip_kind, dim3((unsigned)L.grid[BT_K1]), s, grad, mmt, vec, b->momentum, w, arg,
+    launch_k1<false>(b->nesterov != 0, clip_kind, 0u, dim3((unsigned)L.grid[BT_K1]), s, grad, mmt, vec, b->momentum, w, arg,
                      (int)write_through(L.nseg * kSeg), OneTable{}, ca);
     DGC_LAUNCHED();
     return DGC_OK;

@@ -6,6 +6,28 @@
 #include "select_tiles.hpp"
 
 namespace dgc {
+// task() that also returns the tensor's first block, blk[t], from the words the search
+// has loaded: the largest entry <= b of the ascending table (blk[0] = 0). K1 would
+// otherwise read it back, one more round trip ahead of its streaming loads.
+__device__ __forceinline__ int task_first(const int32_t* blk, int T, int b, int64_t& b0) {
+    b0 = 0;
+    if (T <= 1) return 0;
+    const int lane = threadIdx.x & 63;
+    int cnt = 0;
+    uint32_t first = 0;
+    for (int i0 = 0; i0 < T; i0 += 64) {
+        const int i = i0 + lane;
+        const int32_t v = i < T ? blk[i] : 0x7FFFFFFF;
+        const bool le = v <= b;
+        const uint64_t m = __ballot(le);
+        cnt += __popcll(m);
+        first = max(first, le ? (uint32_t)v : 0u);
+        if (m != ~0ull) break;   // ascending table: every later entry is > b
+    }
+    b0 = wave_max(first);
+    return __builtin_amdgcn_readfirstlane(cnt - 1);
+}
+
 // K1 (compensate + strided sample, see compensate.hip) that also lists every
 // element with |vec_new| >= t_list into its segment's list. One wave per segment:
 // float4 index = 256*seg + 64*u + lane (u = 0..3), each instruction 1 KB contiguous;
@@ -14,18 +36,101 @@ namespace dgc {
 // ONE (a one-tensor call): the tensor's tables ride in the arguments (ot) — block 0
 // writes them into the workspace for the kernels after K1, which replaces a k_put_one
 // launch before every K1 (and its wait) — and the sample start in sc.
-// CLIP: the gradient clipped as it is loaded (dgc_common.hpp clip1), tensor t's
+// CLIP: the gradient clipped as it is used (dgc_common.hpp clip1), tensor t's
 // coefficient from ca; DGC_CLIP_NONE compiles to the unclipped kernel.
+//
+// The order of a wave's memory reads is the kernel's schedule (DESIGN.md §5 "K1's
+// schedule", tools/k1_isa.py): every state word it will need (the speculation thresholds,
+// the SelState fields, the deferred masking's offsets, a large batch's table entries) is
+// an independent load of a wave-uniform address ahead of any store of the kernel, so a
+// scalar load on its own counter, and its twelve 16-B streaming loads go out through
+// global-typed pointers before the first use of either kind (the compiler places the
+// scalar loads right behind the streaming ones). A one-tensor wave so waits for nothing
+// but its arguments until 12 KB are in flight. How many such waves a CU holds is the
+// launch's business (select.hip, kK1FlatLds).
+//
+// A null spec or clip table is replaced by the tensor's own state as "any readable words":
+// the kernel then reads words 0 and 2 of SelState and ignores them.
+static_assert(offsetof(SelState, t0) == 0 && offsetof(SelState, t_list) == 2 * sizeof(float),
+              "K1's stand-in for a null spec reads SelState words 0 and 2");
 template <bool NEST, bool ONE, int CLIP>
 __global__ void __launch_bounds__(kBlock)
 k_compensate_list(const float* __restrict__ g_flat, float* __restrict__ mmt_flat, float* __restrict__ vec_flat,
                   float mom, SelWS w, StartChunk sc, int wt, OneTable ot, ClipArg ca) {
-    const int t = ONE ? 0 : task(w, BT_K1, blockIdx.x);
+    int64_t b0 = 0;   // the tensor's first block
+    const int t = ONE ? 0 : task_first(w.bt[BT_K1], w.T, blockIdx.x, b0);
     const TDesc d = ONE ? ot.d : w.td[t];   // by value: stores below cannot alias it
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t b0 = ONE ? 0 : w.bt[BT_K1][t];   // the tensor's first block
+    const int lane = threadIdx.x & 63, wave = wave_id();
     const int64_t ls = ((int64_t)blockIdx.x - b0) * kSegPerBlock4 + wave;   // local segment
-    if (ONE && blockIdx.x == 0 && threadIdx.x == 0) {
+    // a wave past the tensor's last segment loads nothing and lists nothing (no early
+    // exit: a branch here would split the table reads into two round trips)
+    const bool live = ls < d.nseg;
+    const bool first = blockIdx.x == b0 && threadIdx.x == 0;
+    // sample starts (and gradient pointers) of the first sc.count tensors ride in the arguments
+    const bool arg_start = ONE || t < sc.count;
+    const bool ptrs = !ONE && sc.ptrs;   // a one-tensor call reads the flat gradient
+    const bool sample = d.samp_off >= 0;
+
+    // ---- the state words, one batch (uses further down)
+    DGC_GLB SelState* st = glb(w.st + t);
+    DGC_GLB const float* spec = w.spec ? glb(w.spec + kSpecWords * t) : &st->t0;   // (null: any readable words)
+    const float spec0 = spec[0], spec2 = spec[2];
+    const int32_t epoch = st->epoch, def_mode = st->def_mode, def_mask_mmt = st->def_mask_mmt;
+    const float def_t = st->def_t;
+    const long long def_limit = st->def_limit;
+    // the deferred masking's offsets: the slots exist for ls < d.nseg whether or not a
+    // masking is pending. A one-tensor call has their addresses from its arguments; a
+    // batch has them from td[t], which its streaming loads wait for too, so there they
+    // go out right behind the streaming loads instead of one round trip ahead of them
+    const int64_t lsd = live ? ls : 0;
+    DGC_GLB const long long* grp_off = glb(w.grp_off) + (d.grp0 + lsd / kGroupSegs);
+    DGC_GLB const uint32_t* seg_off = glb(w.seg_off) + (d.seg0 + lsd);
+    long long def_rank = 0;
+    if (ONE) def_rank = *grp_off + (long long)*seg_off;
+    float cf_tab = 0.f;
+    if (CLIP != DGC_CLIP_NONE) cf_tab = *(ca.tab ? glb(ca.tab + t) : (DGC_GLB const float*)&st->t0);
+    int64_t start_ws = 0, scnt_ws = 0;
+    const float* gptr_ws = nullptr;
+    if (!arg_start) {   // a batch past 64 tensors: k_put_starts wrote them
+        start_ws = glb(w.starts)[t];
+        scnt_ws = glb(w.scnt)[t];
+        if (ptrs) gptr_ws = glb(w.gptr)[t];
+    }
+
+    // ---- the streaming loads: momentum and velocity, then the gradient (its pointer may
+    // be one of the words above)
+    const int64_t n = d.n;
+    const int64_t seg4 = ls * (kSeg / 4);
+    const int left = (int)min(d.nv4 - seg4, (int64_t)(kSeg / 4));   // float4s of the segment
+    // a pointer-table gradient is exactly n floats: its full float4s only
+    const int gleft = ptrs ? (int)min((n >> 2) - seg4, (int64_t)(kSeg / 4)) : left;
+    DGC_GLB float4* mmt = glb(reinterpret_cast<float4*>(mmt_flat + d.off) + seg4);
+    DGC_GLB float4* vec = glb(reinterpret_cast<float4*>(vec_flat + d.off) + seg4);
+    const float* gsrc = !ptrs ? g_flat + d.off : (arg_start ? sc.grad[ONE ? 0 : t] : gptr_ws);
+    DGC_GLB const float4* g = glb(reinterpret_cast<const float4*>(gsrc) + seg4);
+    float4 gv[kSegTiles], mv[kSegTiles], vv[kSegTiles];
+#pragma unroll
+    for (int u = 0; u < kSegTiles; ++u) {
+        if (u * 64 + lane < left) {
+            mv[u] = ld_nt(mmt + u * 64 + lane);
+            vv[u] = ld_nt(vec + u * 64 + lane);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < kSegTiles; ++u)
+        if (u * 64 + lane < gleft) gv[u] = ld_nt(g + u * 64 + lane);
+    // the one wave that owns the partial last float4 of a pointer-table gradient patches
+    // it in (wave-uniform branch, one lane loads)
+    if (ptrs && gleft < left && gleft >= 0) {
+#pragma unroll
+        for (int u = 0; u < kSegTiles; ++u)
+            if (u * 64 + lane == gleft) gv[u] = ld_tail4(glb(gsrc), n);
+    }
+
+    if (!ONE) def_rank = *grp_off + (long long)*seg_off;
+
+    // ---- everything loaded is in flight: the stores of the call's tables
+    if (ONE && first) {
         w.td[0] = ot.d;
         for (int which = 0; which < BT_COUNT; ++which) {
             w.bt[which][0] = ot.bt[which][0];
@@ -33,21 +138,13 @@ k_compensate_list(const float* __restrict__ g_flat, float* __restrict__ mmt_flat
         }
         w.small[0] = 0;
     }
-    // sample starts (and gradient pointers) of the first sc.count tensors ride in the arguments
-    const bool arg_start = t < sc.count;
-    const float* gsrc = !sc.ptrs ? g_flat + d.off : (arg_start ? sc.grad[t] : w.gptr[t]);
-    const float4* g = reinterpret_cast<const float4*>(gsrc);
-    float4* mmt = reinterpret_cast<float4*>(mmt_flat + d.off);
-    float4* vec = reinterpret_cast<float4*>(vec_flat + d.off);
-    const int64_t n4 = d.nv4, n = d.n;
-    const float tl = w.spec ? w.spec[kSpecWords * t] : __builtin_huge_valf();
-    SelState* st = w.st + t;
-    if (blockIdx.x == b0 && threadIdx.x == 0) st->t_list = tl;
-    const bool sample = d.samp_off >= 0;
-    const int64_t start = !sample ? 0 : (arg_start ? sc.start[t] : w.starts[t]);
-    const int64_t scount = !sample ? 0 : (arg_start ? ceil_div(d.n - start, d.stride) : w.scnt[t]);
-    if (arg_start && blockIdx.x == b0 && threadIdx.x == 0) {
-        w.starts[t] = sc.start[t];
+    const float tl = w.spec ? spec0 : __builtin_huge_valf();
+    const float cf = ca.tab ? cf_tab : ca.value;
+    if (first) st->t_list = tl;
+    const int64_t start = !sample ? 0 : (arg_start ? sc.start[ONE ? 0 : t] : start_ws);
+    const int64_t scount = !sample ? 0 : (arg_start ? ceil_div(d.n - start, d.stride) : scnt_ws);
+    if (arg_start && first) {
+        w.starts[t] = start;
         w.scnt[t] = sample ? scount : d.n;
     }
     float* sout = sample ? w.samples + d.samp_off : nullptr;
@@ -55,48 +152,35 @@ k_compensate_list(const float* __restrict__ g_flat, float* __restrict__ mmt_flat
     // prediction of this call's sampled threshold, just below it; the list threshold
     // before the first prediction), inf and NaN too
     float* win = w.samples + d.win_off;
-    const float tw = w.spec ? w.spec[kSpecWords * t + 2] : __builtin_huge_valf();
+    const float tw = w.spec ? spec2 : __builtin_huge_valf();
     const uint32_t win_key = abs_key(tw < __builtin_huge_valf() ? tw : tl);
     const bool windowed = sample && d.win_cap > 0;
-    uint32_t* win_cnt = &st->win_cnt[st->epoch & 1];
+    uint32_t* win_cnt = &w.st[t].win_cnt[epoch & 1];
     uint32_t* whist = reinterpret_cast<uint32_t*>(w.samples + d.whist_off);
-    if (windowed && blockIdx.x == b0 && threadIdx.x == 0) st->win_key = win_key;
-    // waves past the tensor's last segment load nothing and list nothing, but stay for
-    // the block barrier of the spill count
+    if (windowed && first) st->win_key = win_key;
     int64_t q0 = 0, r0 = 0;
     if (sample) floor_divmod_fast(ls * kSeg - start, d.stride, d.inv_stride, q0, r0);
-    float4 gv[kSegTiles], mv[kSegTiles], vv[kSegTiles];
-    const float cf = clip_coef<CLIP>(ca, t);
-#pragma unroll
-    for (int u = 0; u < kSegTiles; ++u) {
-        const int64_t v = ls * (kSeg / 4) + u * 64 + lane;
-        if (v < n4) {
-            gv[u] = clip4<CLIP>(sc.ptrs && 4 * v + 3 >= n ? ld_tail4(gsrc, 4 * v, n) : ld_nt(g + v), cf);
-            mv[u] = ld_nt(mmt + v);
-            vv[u] = ld_nt(vec + v);
-        }
-    }
     uint32_t c = 0, mk = 0;
     const int64_t seg = d.seg0 + ls;
     uint16_t* lo = w.lst_off;
     float* lv = w.lst_val;
-    if (st->def_mode && ls < d.nseg) apply_deferred_mask(*st, w, d, ls, lane, vv, mv);
+    if (def_mode && live) apply_deferred_mask(def_t, def_limit, def_mask_mmt != 0, def_rank, d, ls, lane, vv, mv);
 #pragma unroll
     for (int u = 0; u < kSegTiles; ++u) {
-        const int64_t v = ls * (kSeg / 4) + u * 64 + lane;
-        const bool ok = v < n4;
+        const bool ok = u * 64 + lane < left;
         float x[4] = {0.f, 0.f, 0.f, 0.f};
         uint32_t valid = 0;
         bool hit = false;   // this lane's sample (at most one per float4: stride >= 4) joins the window
         float hv = 0.f;
         if (ok) {
-            x[0] = comp1<NEST, true>(gv[u].x, mv[u].x, vv[u].x, mom);
-            x[1] = comp1<NEST, true>(gv[u].y, mv[u].y, vv[u].y, mom);
-            x[2] = comp1<NEST, true>(gv[u].z, mv[u].z, vv[u].z, mom);
-            x[3] = comp1<NEST, true>(gv[u].w, mv[u].w, vv[u].w, mom);
-            st_stream(mmt + v, mv[u], wt);
-            st_stream(vec + v, vv[u], wt);
-            const int64_t e = 4 * v;
+            const float4 gq = clip4<CLIP>(gv[u], cf);
+            x[0] = comp1<NEST, true>(gq.x, mv[u].x, vv[u].x, mom);
+            x[1] = comp1<NEST, true>(gq.y, mv[u].y, vv[u].y, mom);
+            x[2] = comp1<NEST, true>(gq.z, mv[u].z, vv[u].z, mom);
+            x[3] = comp1<NEST, true>(gq.w, mv[u].w, vv[u].w, mom);
+            st_stream(mmt + u * 64 + lane, mv[u], wt);
+            st_stream(vec + u * 64 + lane, vv[u], wt);
+            const int64_t e = 4 * (seg4 + u * 64 + lane);
             valid = e + 3 < n ? 0xFu : (e + 2 < n ? 7u : (e + 1 < n ? 3u : (e < n ? 1u : 0u)));
             if (sample) {
                 const uint32_t tt = (uint32_t)r0 + 4u * (uint32_t)(u * 64 + lane);
@@ -127,20 +211,13 @@ k_compensate_list(const float* __restrict__ g_flat, float* __restrict__ mmt_flat
         list_append(ge_mask(x, valid, tl), x, u * 256, c, lo, lv, seg);
         mk = max(mk, tile_max_key(x, valid));
     }
-    const bool spilled = c > (uint32_t)kCap;
     mk = wave_max(mk);
-    if (lane == 0 && ls < d.nseg) {
+    if (lane == 0 && live) {
         const bool tail = d.tail && ls == d.nseg - 1;   // its scalar tail is compensated outside K1
         w.seg_lcnt[seg] = tail ? lcnt_pack(kCap + 1, 0xFFFFu) : lcnt_pack(c, lmax_code(mk));
+        // one atomic per wave with a spilled segment (c is wave-uniform; shard by block)
+        if (c > (uint32_t)kCap) atomicAdd(&w.st[t].spill[epoch & 1][blockIdx.x % kSpillShards], 1u);
     }
-    // one atomic per workgroup with a spilled segment (shard by block)
-    const uint64_t any = __ballot(spilled);
-    __shared__ uint32_t nsp;
-    if (threadIdx.x == 0) nsp = 0;
-    __syncthreads();
-    if (lane == 0 && any) atomicAdd(&nsp, 1u);
-    __syncthreads();
-    if (threadIdx.x == 0 && nsp) atomicAdd(&st->spill[st->epoch & 1][blockIdx.x % kSpillShards], nsp);
 }
 
 __global__ void k_no_lists(SelWS w) {

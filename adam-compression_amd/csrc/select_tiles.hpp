@@ -7,11 +7,13 @@
 #include "select_layout.hpp"
 
 namespace dgc {
-// The float4 at element e0 of a gradient of n elements that may end inside it (a
-// pointer-table gradient is exactly n floats long): elements past n read as 0.
-__device__ __forceinline__ float4 ld_tail4(const float* __restrict__ g, int64_t e0, int64_t n) {
-    if (e0 + 3 < n) return ld_nt(reinterpret_cast<const float4*>(g + e0));
-    return make_float4(g[e0], e0 + 1 < n ? g[e0 + 1] : 0.f, e0 + 2 < n ? g[e0 + 2] : 0.f, 0.f);
+// The last float4 of a pointer-table gradient that ends inside it (exactly n floats long,
+// n & 3 of them in this float4, which starts at element 4 * (n / 4)): elements past n
+// read as 0. Scalar loads: a 16-B load would run past the gradient's end.
+__device__ __forceinline__ float4 ld_tail4(DGC_GLB const float* g, int64_t n) {
+    DGC_GLB const float* p = g + (n & ~(int64_t)3);
+    const int r = (int)(n & 3);
+    return make_float4(p[0], r > 1 ? p[1] : 0.f, r > 2 ? p[2] : 0.f, 0.f);
 }
 
 // Upper bound of a segment's largest |x| key, in 16-bit units: every key < code << 16.
@@ -112,16 +114,13 @@ __device__ uint32_t wave_count_segment(const float* __restrict__ v, int64_t n, i
 __device__ __forceinline__ int task(const SelWS& w, int which, int b) { return task_of_block(w.bt[which], w.T, b); }
 
 // The last call's deferred masking for one segment (one wave): zero, in the loaded
-// tiles, the elements that call emitted — the first def_limit elements (flat
-// order) with |vec| >= def_t, ranked by grp_off + seg_off + in-segment rank. vec is
-// unchanged since that emit, so the recount reproduces its choice exactly.
-__device__ __forceinline__ void apply_deferred_mask(const SelState& st, const SelWS& w, const TDesc& d,
-                                                    int64_t ls, int lane, float4 (&vv)[kSegTiles],
+// tiles, the elements that call emitted — the first dlim elements (flat order) with
+// |vec| >= dt, ranked from `rank` (the segment's grp_off + seg_off) by in-segment rank.
+// vec is unchanged since that emit, so the recount reproduces its choice exactly. The
+// caller passes the state words by value: K1 loads them ahead of its streaming loads.
+__device__ __forceinline__ void apply_deferred_mask(float dt, long long dlim, bool mm, long long rank,
+                                                    const TDesc& d, int64_t ls, int lane, float4 (&vv)[kSegTiles],
                                                     float4 (&mv)[kSegTiles]) {
-    const float dt = st.def_t;
-    const long long dlim = st.def_limit;
-    const bool mm = st.def_mask_mmt != 0;
-    long long rank = w.grp_off[d.grp0 + ls / kGroupSegs] + w.seg_off[d.seg0 + ls];
 #pragma unroll
     for (int u = 0; u < kSegTiles; ++u) {
         if (rank >= dlim) break;   // wave-uniform
