@@ -17,7 +17,11 @@
 //          order (indices within one rank's payload are distinct, as DGC emits them),
 //          then one pass scales.
 // HBM: K1-16 moves 10 B/elem (+4 for the image). Not a BASELINE configuration (every
-// benched config is fp32). The batch (DGCBatch / DistributedOptimizer(batch=True) on
+// benched config is fp32). k_compensate16 is the correctness port: scalar 2-B accesses, no
+// samples, no candidate lists. The flat bucket's K1-16 (DGCBucket(dtype=...),
+// k_compensate_list16 in select_k1_16.hpp) is the vectorised one that fuses the strided
+// sample, the sample window and the lists; the per-tensor path and the batch stay on this
+// kernel. The batch (DGCBatch / DistributedOptimizer(batch=True) on
 // 16-bit parameters) runs K1-16 over its flat 16-bit buffers, dgc_batch_select on the
 // image, k_mask_packed16 / k_scatter_packed16 from the packed payloads (their counts
 // read on the device), k_gather16 for the optimizer's p.grad tensors.

@@ -56,6 +56,7 @@
 #include "select_layout.hpp"       // host layout, workspace carve, k_put_one / k_put_starts
 #include "select_tiles.hpp"        // tile loads, list append, task(), deferred masking
 #include "select_k1.hpp"           // K1 with lists
+#include "select_k1_16.hpp"        // K1 with lists over 16-bit state (the flat bucket)
 #include "select_state.hpp"        // sel_init_tensor, decide_tensor
 #include "select_thresholds.hpp"   // K3
 #include "select_count.hpp"        // list count, select pass, lowering
@@ -642,13 +643,76 @@ int compress_begin(const float* grad, float* mmt, float* vec, float momentum, bo
     return DGC_OK;
 }
 
+// K1-16 of the flat bucket: 16-bit momentum / velocity / gradient, the velocity's fp32
+// image vec32 (+ fused strided sample + speculative candidate lists, all from the image);
+// dgc_compress_finish(vec32, null, ...) then serves the image. mmt, vec and vec32 hold
+// ceil(numel / 1024) * 1024 elements. There is no unfused fallback: what the listing
+// kernel cannot take is refused.
+template <int DT>
+static void launch_k1_16(bool nesterov, dim3 gd, hipStream_t s, const uint16_t* grad, uint16_t* mmt,
+                         uint16_t* vec, float* vec32, float momentum, const SelWS& w, int64_t start, int wt,
+                         const OneTable& ot) {
+    if (nesterov)
+        hipLaunchKernelGGL((k_compensate_list16<DT, true>), gd, dim3(kBlock), 0, s, grad, mmt, vec, vec32, momentum,
+                           w, start, wt, ot);
+    else
+        hipLaunchKernelGGL((k_compensate_list16<DT, false>), gd, dim3(kBlock), 0, s, grad, mmt, vec, vec32, momentum,
+                           w, start, wt, ot);
+}
+
+int compress_begin16(const void* grad, void* mmt, void* vec, float* vec32, float momentum, bool nesterov,
+                     int64_t s_start, int64_t s_stride, const dgc_select_params* p, float* spec, void* ws,
+                     size_t ws_bytes, int32_t dtype, hipStream_t s) {
+    if (dtype != DGC_BF16 && dtype != DGC_F16)
+        DGC_FAIL(DGC_ERR_INVALID, "dgc_compress_begin16: dtype must be DGC_BF16 or DGC_F16 (got %d)", (int)dtype);
+    if (!grad || !mmt || !vec || !vec32 || !p)
+        DGC_FAIL(DGC_ERR_INVALID, "dgc_compress_begin16: null grad/mmt/vec/vec32/params");
+    if (p->update_memory != 0)
+        DGC_FAIL(DGC_ERR_INVALID, "dgc_compress_begin16: update_memory must be 0 (the 16-bit state is masked from "
+                                  "the payload, dgc_mask_packed16)");
+    if (p->thr_dtype != dtype)
+        DGC_FAIL(DGC_ERR_INVALID, "dgc_compress_begin16: params.thr_dtype %d must be the dtype %d", (int)p->thr_dtype,
+                 (int)dtype);
+    DGC_TRY(compress_check(p, nullptr, nullptr, s_start, s_stride, 1, false));
+    const int64_t n = p->numel;
+    const bool sampled = n != p->num_samples;
+    if (!aligned16(grad) || !aligned16(mmt) || !aligned16(vec) || !aligned16(vec32))
+        DGC_FAIL(DGC_ERR_INVALID, "dgc_compress_begin16: grad, mmt, vec and vec32 must be 16-B aligned");
+    if (sampled && (s_stride < 4 || s_stride >= (1LL << 30)))
+        DGC_FAIL(DGC_ERR_INVALID, "dgc_compress_begin16: sample stride %lld outside [4, 2^30)", (long long)s_stride);
+    Layout L;
+    SelWS w;
+    OneTable ot{};
+    DGC_TRY(one_ws(p, s_start, s_stride, 1, spec, ws, ws_bytes, L, w, ot));
+    if (L.grid[BT_K1] < 1 || L.grid[BT_K1] > 0x7FFFFFFFLL)
+        DGC_FAIL(DGC_ERR_INVALID, "dgc_compress_begin16: n too large");
+    // No kK1FlatLds here: a wave of this kernel has 6 KB of loads in flight where the fp32
+    // one has 12, and held to 3 waves per SIMD it ran slower. Same box, 1e9 elements, K1-16
+    // ms: 3 waves (48 KB of LDS asked for) 2.47-2.49, 6 waves (24 KB) 2.28, the registers'
+    // 7 waves 2.28; two segments per wave (24 loads in flight) 2.42 / 2.33 / 2.33 at the
+    // same three (DESIGN.md §5 "The 16-bit flat bucket").
+    const bool wt = write_through(n);
+    const dim3 gd((unsigned)L.grid[BT_K1]);
+    const uint16_t* g16 = static_cast<const uint16_t*>(grad);
+    uint16_t *m16 = static_cast<uint16_t*>(mmt), *v16 = static_cast<uint16_t*>(vec);
+    if (dtype == DGC_BF16)
+        launch_k1_16<DGC_BF16>(nesterov, gd, s, g16, m16, v16, vec32, momentum, w, ot.start, (int)wt, ot);
+    else
+        launch_k1_16<DGC_F16>(nesterov, gd, s, g16, m16, v16, vec32, momentum, w, ot.start, (int)wt, ot);
+    DGC_LAUNCHED();
+    return DGC_OK;
+}
+
 // K3 threshold over the samples, then the selection (lists kept from begin).
 int compress_finish(float* vec, float* mmt, int64_t s_start, int64_t s_stride, int64_t top_k_samples,
                     const dgc_select_params* p, float* spec, float margin, void* values, void* indices,
                     int64_t* count_out, dgc_select_info* info, void* ws, size_t ws_bytes, int sync_mode,
                     hipStream_t s) {
     DGC_TRY(compress_check(p, values, indices, s_start, s_stride, top_k_samples, true));
-    if (!vec || (p->masking && !mmt)) DGC_FAIL(DGC_ERR_INVALID, "dgc_compress: null vec/mmt");
+    // update_memory 0 with masking set and no momentum to mask: the pure selection of a
+    // 16-bit bucket's fp32 image (dgc_compress_begin16), which writes neither vec nor mmt
+    const bool pure = p->update_memory == 0 && p->masking && !mmt;
+    if (!vec || (p->masking && !mmt && !pure)) DGC_FAIL(DGC_ERR_INVALID, "dgc_compress: null vec/mmt");
     Layout L;
     SelWS w;
     OneTable ot{};
@@ -658,7 +722,7 @@ int compress_finish(float* vec, float* mmt, int64_t s_start, int64_t s_stride, i
     DGC_TRY(thresholds(w, L, vec, s, top_k_samples));
     dgc_select_params q = *p;
     // DGCSGDMemory.update fused into the emit (1), or deferred into the next K1 (2)
-    q.update_memory = p->update_memory == 2 ? 2 : 1;
+    q.update_memory = pure ? 0 : (p->update_memory == 2 ? 2 : 1);
     return select_core(vec, mmt, cfg_of(q), L, values, indices, count_out, info, w, 1, sync_mode, margin,
                        p->status_sink, p->order_out, s);
 }
@@ -938,6 +1002,15 @@ extern "C" int dgc_compress_begin(const float* grad, float* mmt, float* vec, flo
     // begin only reads spec[0] (the list threshold); finish updates it
     return dgc::compress_begin(grad, mmt, vec, momentum, nesterov != 0, sample_start, sample_stride, params,
                                const_cast<float*>(spec_threshold), ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int dgc_compress_begin16(const void* grad, void* mmt, void* vec, float* vec32, float momentum,
+                                    int32_t nesterov, int64_t sample_start, int64_t sample_stride,
+                                    const dgc_select_params* params, const float* spec_threshold, void* ws,
+                                    size_t ws_bytes, int32_t dtype, void* stream) {
+    return dgc::compress_begin16(grad, mmt, vec, vec32, momentum, nesterov != 0, sample_start, sample_stride, params,
+                                 const_cast<float*>(spec_threshold), ws, ws_bytes, dtype,
+                                 static_cast<hipStream_t>(stream));
 }
 
 extern "C" int dgc_compress_finish(float* vec, float* mmt, int64_t sample_start, int64_t sample_stride,

@@ -204,6 +204,8 @@ _SIGNATURES = {
                                     _P, _F, _P, _P, _P, _P, _P, _SZ, _I32, _P]),
     "dgc_compress_begin": (ctypes.c_int, [_P, _P, _P, _F, _I32, _I64, _I64, ctypes.POINTER(SelectParams), _P, _P,
                                           _SZ, _P]),
+    "dgc_compress_begin16": (ctypes.c_int, [_P, _P, _P, _P, _F, _I32, _I64, _I64, ctypes.POINTER(SelectParams), _P,
+                                            _P, _SZ, _I32, _P]),
     "dgc_compress_finish": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, ctypes.POINTER(SelectParams), _P, _F, _P, _P,
                                            _P, _P, _P, _SZ, _I32, _P]),
     "dgc_compress_flush": (ctypes.c_int, [_P, _P, _I64, ctypes.POINTER(SelectParams), _P, _SZ, _P]),

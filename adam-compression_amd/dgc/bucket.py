@@ -1,7 +1,7 @@
 """Flat-bucket DGC step with no host synchronisation (the padded fast path).
 
-One fp32 gradient bucket per rank goes through the whole DGC step of the
-reference — compensate -> sample -> threshold -> select/adapt/resample -> update
+One gradient bucket per rank (fp32, or bf16 / fp16 with ``dtype``) goes through the
+whole DGC step of the reference — compensate -> sample -> threshold -> select/adapt/resample -> update
 (dgc/memory.py:50-77, dgc/compression.py:109-177) -> allgather
 (dgc/compression.py:200-212) -> decompress (dgc/compression.py:179-194) — with
 every decision kept on the device:
@@ -25,6 +25,14 @@ every decision kept on the device:
   out in parts and each part is scattered as it lands, so only the last part's share
   of the W-dependent scatter is exposed after the exchange.
 
+``dtype=torch.bfloat16`` / ``torch.float16``: momentum, velocity, gradient and output are
+16-bit, every op of the reference rounded to the dtype as on the per-tensor path. K1-16
+(``dgc_compress_begin16``) streams the 16-bit state, writes the new velocity's exact fp32
+image and takes the samples and the candidate lists from it; the selection then runs
+pure on the image and the 16-bit state is masked from the payload
+(``dgc_mask_packed16``), so nothing is ever deferred. The receive side is the 16-bit
+packed decompress (``dgc_decompress_packed16``: dense fill, one exchange part).
+
 The numerics are those of the drop-in ``DGCCompressor`` + ``DGCSGDMemory`` (same
 kernels); the sample start is drawn from a ``random.Random`` seeded identically on
 every rank, one draw per step, like the reference's global ``random`` call.
@@ -42,12 +50,19 @@ from .exchange import ReceiveSide, Receiver
 
 __all__ = ["DGCBucket", "algorithmic_bytes"]
 
+SEG = 1024   # the kernels' segment: a 16-bit bucket pads its state to whole segments
 
-def algorithmic_bytes(numel, k, num_samples, world, vbytes=4, ibytes=8):
+
+def algorithmic_bytes(numel, k, num_samples, world, vbytes=4, ibytes=8, sbytes=4):
     """Bytes one rank must move per step:
     compensate 20N + select re-read 4N + dense decompress write 4N, the samples 4S,
-    masking 8k, payload written k(vb+ib) + gathered W*k(vb+ib) read, scatter RMW 8Wk."""
-    return (28 * numel + 4 * num_samples + 8 * k + (1 + world) * k * (vbytes + ibytes) + 8 * world * k)
+    masking 8k, payload written k(vb+ib) + gathered W*k(vb+ib) read, scatter RMW 8Wk.
+    sbytes: the state element size. 2 (a 16-bit bucket): compensate 3 x 2N read + 2 x 2N
+    written + the 4N image, the image re-read 4N, the decompress write 2N, masking and
+    scatter 2 B per entry and array."""
+    image = 4 if sbytes < 4 else 0
+    return ((6 * sbytes + image + 4) * numel + 4 * num_samples + 2 * sbytes * k + (1 + world) * k * (vbytes + ibytes)
+            + 2 * sbytes * world * k)
 
 
 class DGCBucket(ReceiveSide):
@@ -55,16 +70,24 @@ class DGCBucket(ReceiveSide):
                  sample_ratio=0.01, compress_upper_bound=1.3, compress_lower_bound=0.8,
                  max_adaptation_iters=10, resample=True, fp16_values=False, int32_indices=False,
                  device=None, world_size=None, seed=42, fill="auto", deferred_masking=True, exchange_parts="auto",
-                 resample_order="topk"):
+                 resample_order="topk", dtype=torch.float32):
         if fill not in ("auto", "inline", "allgather", "sparse"):
             raise ValueError(f"fill must be 'auto', 'inline', 'allgather' or 'sparse', not {fill!r}")
+        if dtype not in (torch.float32,) + _lib.HALF:
+            raise NotImplementedError(f"DGCBucket: fp32, bf16 or fp16 parameters (got {dtype})")
+        self.dtype = dtype
+        self.half = dtype in _lib.HALF
+        if self.half and fill in ("allgather", "sparse"):
+            raise NotImplementedError(f"DGCBucket: fill={fill!r} on {dtype} parameters (the 16-bit decompress is the "
+                                      "dense fill with the scatter)")
         self.device = torch.device(device or "cuda")
         self.numel = N = int(numel)
         self.k, self.num_samples, self.top_k_samples, self.stride = DGCCompressor._attributes(
             N, *DGCCompressor._normalized(compress_ratio, sample_ratio))
         self.momentum, self.nesterov = float(momentum), bool(nesterov)
         self.world = world_size or (dist.get_world_size() if dist.is_initialized() else 1)
-        self.vdtype = torch.float16 if fp16_values else torch.float32
+        self.momentum_masking = bool(momentum_masking)
+        self.vdtype = torch.float16 if fp16_values else dtype
         self.idtype = torch.int32 if int32_indices else torch.int64
         self.rng = random.Random(seed)
 
@@ -78,6 +101,11 @@ class DGCBucket(ReceiveSide):
         # next step's K1, which streams vec/mmt anyway (mmt/vec below flush it on read)
         p.vdtype, p.idtype = _lib.VD[self.vdtype], _lib.ID[self.idtype]
         p.update_memory = 2 if deferred_masking else 1
+        if self.half:
+            # the selection runs pure on the fp32 image (update_memory 0; with masking set and
+            # no momentum dgc_compress_finish writes nothing), its threshold *= bound products
+            # rounded to the dtype; momentum_masking decides what dgc_mask_packed16 masks
+            p.update_memory, p.masking, p.thr_dtype = 0, 1, _lib.VD[dtype]
         # "index" (opt-in): an untied resample lists its set in index order (DGCBatch's
         # default); a flat bucket's resample (up to 64k candidates) mostly exceeds the
         # one-workgroup set path, so it keeps torch.topk's order by default
@@ -87,8 +115,12 @@ class DGCBucket(ReceiveSide):
         self.params = p
 
         dev = self.device
-        self._mmt = torch.zeros(N, dtype=torch.float32, device=dev)
-        self._vec = torch.zeros(N, dtype=torch.float32, device=dev)
+        # 16-bit: state and image padded to whole 1024-element segments (+0, and K1-16 keeps
+        # them so), so the kernel needs no scalar tail on them
+        self.padded = -(-N // SEG) * SEG if self.half else N
+        self._mmt = torch.zeros(self.padded, dtype=dtype, device=dev)
+        self._vec = torch.zeros(self.padded, dtype=dtype, device=dev)
+        self._vec32 = torch.zeros(self.padded, dtype=torch.float32, device=dev) if self.half else None
         self._pending = False
         L = _lib.lib()
         self.sampled = N != self.num_samples
@@ -99,7 +131,7 @@ class DGCBucket(ReceiveSide):
         self.info = torch.zeros(_lib.INFO_BYTES, dtype=torch.uint8, device=dev)
         # the payload and gather buffers, the exchange and the decompress (dgc/exchange.py)
         self.rx = Receiver(self.k, N, self.world, self.vdtype, self.idtype, dev, self.status, fill, exchange_parts,
-                           unsent="DGCBucket: decompress of a split exchange before exchange()")
+                           half=self.half, unsent="DGCBucket: decompress of a split exchange before exchange()")
         self._L = L
         if self.fill in ("allgather", "sparse"):
             self.side = torch.cuda.Stream(device=dev)
@@ -119,13 +151,13 @@ class DGCBucket(ReceiveSide):
     def mmt(self):
         """Momentum (DGCSGDMemory.momentums), masking applied."""
         self.flush()
-        return self._mmt
+        return self._mmt[:self.numel] if self.half else self._mmt
 
     @property
     def vec(self):
         """Velocity (DGCSGDMemory.velocities), masking applied."""
         self.flush()
-        return self._vec
+        return self._vec[:self.numel] if self.half else self._vec
 
     # ---------------------------------------------------------------- phases
     def compensate(self, grad):
@@ -136,11 +168,23 @@ class DGCBucket(ReceiveSide):
         L = self._L
         self.rx.begin()
         self.start = self.rng.randint(0, self.stride - 1) if self.sampled else 0
+        self.cnt = (self.numel - self.start + self.stride - 1) // self.stride if self.sampled else self.numel
+        if self.half:
+            # exactly N elements of the dtype: K1-16 reads the gradient to its last element
+            if not (torch.is_tensor(grad) and grad.is_cuda and grad.dtype == self.dtype and grad.is_contiguous()
+                    and grad.numel() == self.numel and grad.data_ptr() % 16 == 0):
+                raise ValueError(f"DGCBucket.compensate: grad must be a contiguous, 16-B aligned {self.dtype} CUDA "
+                                 f"tensor of {self.numel} elements")
+            _lib.check(L.dgc_compress_begin16(grad.data_ptr(), self._mmt.data_ptr(), self._vec.data_ptr(),
+                                              self._vec32.data_ptr(), self.momentum, int(self.nesterov), self.start,
+                                              self.stride, ctypes.byref(self.params), self.spec.data_ptr(),
+                                              self.ws.data_ptr(), self.ws.numel(), _lib.VD[self.dtype],
+                                              _lib.stream_of(self.device)), "dgc_compress_begin16")
+            return
         _lib.check(L.dgc_compress_begin(grad.data_ptr(), self._mmt.data_ptr(), self._vec.data_ptr(), self.momentum,
                                         int(self.nesterov), self.start, self.stride, ctypes.byref(self.params),
                                         self.spec.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
                                         _lib.stream_of(self.device)), "dgc_compress_begin")
-        self.cnt = (self.numel - self.start + self.stride - 1) // self.stride if self.sampled else self.numel
         self._pending = False   # K1 applied it
 
     def select(self):
@@ -148,6 +192,17 @@ class DGCBucket(ReceiveSide):
         L = self._L
         base = self.payload.data_ptr()
         self.params.order_out = base + 8   # header word 1: the W = 1 scatter's ascending-order flag
+        if self.half:   # the pure selection on the image, then DGCSGDMemory.update on the 16-bit state
+            st = _lib.stream_of(self.device)
+            _lib.check(L.dgc_compress_finish(self._vec32.data_ptr(), None, self.start, self.stride, self.top_k_samples,
+                                             ctypes.byref(self.params), self.spec.data_ptr(), _lib.SPEC_MARGIN,
+                                             base + self.voff, base + self.ioff, base, self.info.data_ptr(),
+                                             self.ws.data_ptr(), self.ws.numel(), _lib.SYNC_DEVICE, st),
+                       "dgc_compress_finish")
+            _lib.check(L.dgc_mask_packed16(base, self.k, _lib.VD[self.vdtype], _lib.ID[self.idtype],
+                                           self._mmt.data_ptr() if self.momentum_masking else None,
+                                           self._vec.data_ptr(), self.numel, st), "dgc_mask_packed16")
+            return
         self._pending = self.params.update_memory == 2
         _lib.check(L.dgc_compress_finish(self._vec.data_ptr(), self._mmt.data_ptr(), self.start, self.stride,
                                          self.top_k_samples, ctypes.byref(self.params), self.spec.data_ptr(),
@@ -159,7 +214,22 @@ class DGCBucket(ReceiveSide):
         """dense: out = scale * (rank-order sum of the gathered entries), zeros elsewhere.
         dense=False: out already holds +0.0 (see ``Receiver.zero``); only the entries are
         written. fill="sparse": a dense decompress into the previous step's untouched
-        output re-zeroes only the previous entries (see ``Receiver``)."""
+        output re-zeroes only the previous entries (see ``Receiver``). A 16-bit bucket:
+        zero_(), the runs in rank order (each add rounded to the dtype), the 1/W scale."""
+        if self.half:
+            if not dense:
+                raise NotImplementedError(f"DGCBucket.decompress: dense=False on {self.dtype} parameters")
+            if _lib.require_cuda_float(out, "DGCBucket.decompress") != self.dtype or out.numel() != self.numel \
+                    or out.device != self.device:
+                raise ValueError(f"DGCBucket.decompress: out must be a contiguous {self.dtype} tensor of "
+                                 f"{self.numel} elements on {self.device} (got {out.dtype} [{out.numel()}] on "
+                                 f"{out.device})")
+            self.rx.wait()
+            _lib.check(self._L.dgc_decompress_packed16(
+                self.gathered.data_ptr(), self.world, self.rank_stride, self.k, _lib.VD[self.vdtype],
+                _lib.ID[self.idtype], out.data_ptr(), _lib.VD[self.dtype], self.numel, 1.0 / self.world,
+                ctypes.c_void_p(self.status.decompress_words), _lib.stream_of(self.device)), "dgc_decompress_packed16")
+            return
         if dense:
             self.rx.decompress(out)
         else:
@@ -194,7 +264,9 @@ class DGCBucket(ReceiveSide):
             self._zero_on_side(out, True)
 
         def decompress():
-            if cleared or self.fill == "allgather":   # the entries onto the re-zeroed / filled output
+            if self.half:   # always the dense 16-bit decompress
+                self.decompress(out)
+            elif cleared or self.fill == "allgather":   # the entries onto the re-zeroed / filled output
                 torch.cuda.current_stream(self.device).wait_event(self._ev_filled)
                 self.rx.scatter(out, cleared)
             else:

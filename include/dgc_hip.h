@@ -28,6 +28,8 @@
  *                         the same memory / decompress for bf16 / fp16 parameters
  *                         (dgc/memory.py:43-77, dgc/compression.py:179-194 on a
  *                         16-bit tensor: every op rounds to the dtype)
+ *   dgc_compress_begin16  compensate on 16-bit state + strided sample  dgc/memory.py:50-63,
+ *                         (+ the fp32 image and the candidate lists)   dgc/compression.py:113-121
  *
  * Conventions
  *   - All tensor pointers are DEVICE pointers owned by the caller (PyTorch's caching
@@ -547,6 +549,29 @@ int dgc_mask_packed16(const void* payload, int64_t capacity, int32_t vdtype, int
 int dgc_decompress_packed16(const void* payload, int32_t world, int64_t rank_stride, int64_t capacity,
                             int32_t vdtype, int32_t idtype, void* grad, int32_t dtype, int64_t n, float scale,
                             int32_t* bad_flag, void* stream);
+/* The 16-bit flat bucket: dgc_compress_begin for ONE tensor whose momentum, velocity and
+ * gradient are 16-bit (dtype = DGC_BF16 / DGC_F16). One kernel replaces the reference's
+ * compensate on 16-bit state (dgc/memory.py:50-63) and its strided sample
+ * (dgc/compression.py:113-121): dgc_compensate16's arithmetic with vector loads, the new
+ * velocity's exact fp32 image into vec32, and — all taken from the image — the strided
+ * samples, the sample window and the speculative candidate lists of dgc_compress_begin.
+ * It leaves the workspace as dgc_compress_begin would have left it had it run on the
+ * image, so
+ *     dgc_compress_finish(vec32, NULL, ...)      the same params, start, stride, ws
+ * then selects on the image. The selection is pure: params->update_memory must be 0 and
+ * params->thr_dtype the dtype (dgc_compress_finish takes update_memory 0 with masking set
+ * and a null mmt as "write neither vec nor mmt"); mask the 16-bit state from the payload
+ * with dgc_mask_packed16. Size ws with dgc_compress_workspace and zero-fill it before its
+ * first call.
+ *   grad: exactly params->numel elements, never read past them. mmt, vec, vec32: padded
+ *   by the caller to ceil(numel / 1024) * 1024 elements, the padding +0 (it stays +0).
+ *   All four 16-B aligned; a sampled tensor's stride in [4, 2^30).
+ * DGC_ERR_INVALID, before anything is launched, for any other dtype, a null pointer,
+ * update_memory != 0, thr_dtype != dtype, a misaligned pointer or such a stride: there is
+ * no unfused fallback. No clipping, no batch form. */
+int dgc_compress_begin16(const void* grad, void* mmt, void* vec, float* vec32, float momentum, int32_t nesterov,
+                         int64_t sample_start, int64_t sample_stride, const dgc_select_params* params,
+                         const float* spec_threshold, void* ws, size_t ws_bytes, int32_t dtype, void* stream);
 /* bad_flag of dgc_mask_indices16 / dgc_decompress16 / dgc_decompress_packed16: a device
  * or host-mapped int32 that receives 1 when an index is outside [-n, n) (negative ones
  * wrap as in index_put_ / index_fill_; the packed form takes none below 0) and 2 when a
