@@ -568,6 +568,12 @@ static int one_ws(const dgc_select_params* p, int64_t s_start, int64_t s_stride,
 // bucket was measured either way.
 constexpr unsigned kK1FlatLds = 48u << 10;
 
+// The sample strides the listing kernels (K1, K1-16) take: a lane's 4 elements hold at most
+// one sample (stride >= 4), and the per-tile sample's divmod (k1_sample) runs in 32 bits
+// (stride < 2^30). With 16-B alignment of the arrays, the whole condition under which a
+// tensor can take them.
+static bool k1_stride_ok(bool sampled, int64_t stride) { return !sampled || (stride >= 4 && stride < (1LL << 30)); }
+
 template <bool NEST, bool ONE, typename... Args>
 static void launch_k1_clip(int32_t clip_kind, unsigned lds, dim3 gd, hipStream_t s, Args... args) {
     if (clip_kind == DGC_CLIP_SCALE)
@@ -603,8 +609,7 @@ int compress_begin(const float* grad, float* mmt, float* vec, float momentum, bo
     const int64_t n = p->numel;
     const bool sampled = n != p->num_samples;
     const int64_t cnt = sampled ? ceil_div(n - s_start, s_stride) : 0;
-    const bool list_path = aligned16(grad) && aligned16(mmt) && aligned16(vec) &&
-                           (!sampled || (s_stride >= 4 && s_stride < (1LL << 30)));
+    const bool list_path = aligned16(grad) && aligned16(mmt) && aligned16(vec) && k1_stride_ok(sampled, s_stride);
     if (!list_path) {
         hipLaunchKernelGGL(k_put_one, dim3(1), dim3(64), 0, s, w, ot);
         DGC_LAUNCHED();
@@ -678,7 +683,7 @@ int compress_begin16(const void* grad, void* mmt, void* vec, float* vec32, float
     const bool sampled = n != p->num_samples;
     if (!aligned16(grad) || !aligned16(mmt) || !aligned16(vec) || !aligned16(vec32))
         DGC_FAIL(DGC_ERR_INVALID, "dgc_compress_begin16: grad, mmt, vec and vec32 must be 16-B aligned");
-    if (sampled && (s_stride < 4 || s_stride >= (1LL << 30)))
+    if (!k1_stride_ok(sampled, s_stride))
         DGC_FAIL(DGC_ERR_INVALID, "dgc_compress_begin16: sample stride %lld outside [4, 2^30)", (long long)s_stride);
     Layout L;
     SelWS w;
@@ -752,7 +757,7 @@ static int batch_layout(const dgc_batch_desc* b, HostTables& h) {
             std::snprintf(who, sizeof(who), "dgc_batch: tensor %d", t);
             DGC_TRY(check_replay_width(x.n, x.k, who));
         }
-        if (x.n != x.S && (x.stride < 4 || x.stride >= (1LL << 30)))
+        if (!k1_stride_ok(x.n != x.S, x.stride))
             DGC_FAIL(DGC_ERR_INVALID, "dgc_batch: tensor %d: sample stride %lld outside [4, 2^30)", t,
                      (long long)x.stride);
         if (x.off % kSeg || x.off < prev_end)

@@ -28,6 +28,91 @@ __device__ __forceinline__ int task_first(const int32_t* blk, int T, int b, int6
     return __builtin_amdgcn_readfirstlane(cnt - 1);
 }
 
+// ---- The steps K1 and K1-16 (select_k1_16.hpp) share from the moment a tile's new velocity
+// x[4] stands in registers. A one-tensor call's table stores (w.td[0] = ot.d, ...) are not
+// among them: in a helper (SelWS and OneTable by value) they cost the one-tensor kernels
+// registers and a wave per SIMD (DESIGN.md §5 "K1's shared steps"; tools/k1_isa.py shows it).
+
+// Their wave-uniform set-up, once everything a wave loads is in flight. The call's first
+// thread publishes t_list, the window's key and (put_start) the sample start and count.
+struct K1Seg {
+    float tl;            // list threshold spec[0] (inf: no lists)
+    // the sample window: every sample with key >= win_key, inf and NaN too. Its threshold
+    // spec[2] predicts this call's sampled threshold from just below; before the first
+    // prediction it is the list threshold
+    uint32_t win_key;
+    bool windowed;
+    float *sout, *win;
+    uint32_t *win_cnt, *whist;
+    int64_t scount, q0, r0;   // samples; floor divmod of (the segment's first element - start) by the stride
+};
+__device__ __forceinline__ K1Seg k1_segment_begin(const SelWS& w, const TDesc& d, int t, DGC_GLB SelState* st,
+                                                  bool first, bool put_start, float spec0, float spec2,
+                                                  int32_t epoch, int64_t ls, int64_t start, int64_t scount) {
+    const bool sample = d.samp_off >= 0;
+    K1Seg k;
+    k.tl = w.spec ? spec0 : __builtin_huge_valf();
+    if (first) st->t_list = k.tl;
+    if (put_start && first) {
+        w.starts[t] = start;
+        w.scnt[t] = sample ? scount : d.n;
+    }
+    k.sout = sample ? w.samples + d.samp_off : nullptr;
+    k.win = w.samples + d.win_off;
+    const float tw = w.spec ? spec2 : __builtin_huge_valf();
+    k.win_key = abs_key(tw < __builtin_huge_valf() ? tw : k.tl);
+    k.windowed = sample && d.win_cap > 0;
+    k.win_cnt = &w.st[t].win_cnt[epoch & 1];
+    k.whist = reinterpret_cast<uint32_t*>(w.samples + d.whist_off);
+    if (k.windowed && first) st->win_key = k.win_key;
+    k.scount = scount;
+    k.q0 = k.r0 = 0;
+    if (sample) floor_divmod_fast(ls * kSeg - start, d.stride, d.inv_stride, k.q0, k.r0);
+    return k;
+}
+
+// The per-tile sample of a sampled tensor. A lane's group gi (= 64 * u + lane) holds at most
+// one sample (stride >= 4): its element j, the tensor's sample qi. Writes |x[j]| to
+// sout[qi]; returns whether it joins the window (window: this group may), hv its value.
+__device__ __forceinline__ bool k1_sample(const K1Seg& k, const TDesc& d, const float (&x)[4], uint32_t valid,
+                                          int gi, bool window, float& hv) {
+    const uint32_t s32 = (uint32_t)d.stride;
+    uint32_t q1, r;
+    divmod_u32((uint32_t)k.r0 + 4u * (uint32_t)gi, s32, d.inv_stride_f, q1, r);
+    const uint32_t j = r == 0 ? 0u : s32 - r;
+    if (j >= 4 || !((valid >> j) & 1u)) return false;
+    const int64_t qi = k.q0 + q1 + (r == 0 ? 0 : 1);
+    if (qi < 0 || qi >= k.scount) return false;
+    hv = fabsf(x[j]);
+    k.sout[qi] = hv;
+    return window && __float_as_uint(hv) >= k.win_key;
+}
+
+// The window append of a tile's hits: wave-uniform and rare (~3 ks of the S samples), one
+// atomic on the count per wave; the count runs past win_cap when the list overflows.
+__device__ __forceinline__ void k1_window_append(const K1Seg& k, int64_t win_cap, bool hit, float hv, int lane) {
+    const uint64_t hb = __ballot(hit);
+    if (!hb) return;
+    const int leader = __ffsll((unsigned long long)hb) - 1;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(k.win_cnt, (uint32_t)__popcll(hb));
+    base = __shfl(base, leader);
+    const uint32_t pos = base + (uint32_t)__popcll(hb & ((1ull << lane) - 1));
+    if (hit && pos < (uint64_t)win_cap) k.win[pos] = hv;
+    if (hit) atomicAdd(&k.whist[win_bin(__float_as_uint(hv), k.win_key)], 1u);   // (no return value)
+}
+
+// The segment end: its exact count at t_list with the code of its largest key, or the
+// spilled mark of the segment with a scalar tail; one atomic per wave with a spilled segment
+// (c is wave-uniform) into spill, the tensor's shards of this epoch, sharded by block.
+__device__ __forceinline__ void k1_segment_end(uint32_t c, uint32_t mk, bool put, bool tail, uint32_t* seg_lcnt,
+                                               uint32_t* spill) {
+    mk = wave_max(mk);
+    if (!put) return;
+    *seg_lcnt = tail ? lcnt_pack(kCap + 1, 0xFFFFu) : lcnt_pack(c, lmax_code(mk));
+    if (c > (uint32_t)kCap) atomicAdd(&spill[blockIdx.x % kSpillShards], 1u);
+}
+
 // K1 (compensate + strided sample, see compensate.hip) that also lists every
 // element with |vec_new| >= t_list into its segment's list. One wave per segment:
 // float4 index = 256*seg + 64*u + lane (u = 0..3), each instruction 1 KB contiguous;
@@ -138,32 +223,12 @@ k_compensate_list(const float* __restrict__ g_flat, float* __restrict__ mmt_flat
         }
         w.small[0] = 0;
     }
-    const float tl = w.spec ? spec0 : __builtin_huge_valf();
     const float cf = ca.tab ? cf_tab : ca.value;
-    if (first) st->t_list = tl;
     const int64_t start = !sample ? 0 : (arg_start ? sc.start[ONE ? 0 : t] : start_ws);
     const int64_t scount = !sample ? 0 : (arg_start ? ceil_div(d.n - start, d.stride) : scnt_ws);
-    if (arg_start && first) {
-        w.starts[t] = start;
-        w.scnt[t] = sample ? scount : d.n;
-    }
-    float* sout = sample ? w.samples + d.samp_off : nullptr;
-    // the sample window list: every sample with key >= the window threshold spec[2] (a
-    // prediction of this call's sampled threshold, just below it; the list threshold
-    // before the first prediction), inf and NaN too
-    float* win = w.samples + d.win_off;
-    const float tw = w.spec ? spec2 : __builtin_huge_valf();
-    const uint32_t win_key = abs_key(tw < __builtin_huge_valf() ? tw : tl);
-    const bool windowed = sample && d.win_cap > 0;
-    uint32_t* win_cnt = &w.st[t].win_cnt[epoch & 1];
-    uint32_t* whist = reinterpret_cast<uint32_t*>(w.samples + d.whist_off);
-    if (windowed && first) st->win_key = win_key;
-    int64_t q0 = 0, r0 = 0;
-    if (sample) floor_divmod_fast(ls * kSeg - start, d.stride, d.inv_stride, q0, r0);
+    const K1Seg k = k1_segment_begin(w, d, t, st, first, arg_start, spec0, spec2, epoch, ls, start, scount);
     uint32_t c = 0, mk = 0;
     const int64_t seg = d.seg0 + ls;
-    uint16_t* lo = w.lst_off;
-    float* lv = w.lst_val;
     if (def_mode && live) apply_deferred_mask(def_t, def_limit, def_mask_mmt != 0, def_rank, d, ls, lane, vv, mv);
 #pragma unroll
     for (int u = 0; u < kSegTiles; ++u) {
@@ -182,42 +247,14 @@ k_compensate_list(const float* __restrict__ g_flat, float* __restrict__ mmt_flat
             st_stream(vec + u * 64 + lane, vv[u], wt);
             const int64_t e = 4 * (seg4 + u * 64 + lane);
             valid = e + 3 < n ? 0xFu : (e + 2 < n ? 7u : (e + 1 < n ? 3u : (e < n ? 1u : 0u)));
-            if (sample) {
-                const uint32_t tt = (uint32_t)r0 + 4u * (uint32_t)(u * 64 + lane);
-                const uint32_t s32 = (uint32_t)d.stride;
-                uint32_t q1, r;
-                divmod_u32(tt, s32, d.inv_stride_f, q1, r);
-                const uint32_t j = r == 0 ? 0u : s32 - r;
-                if (j < 4 && ((valid >> j) & 1u)) {
-                    const int64_t qi = q0 + q1 + (r == 0 ? 0 : 1);
-                    if (qi >= 0 && qi < scount) {
-                        hv = fabsf(x[j]);
-                        sout[qi] = hv;
-                        hit = windowed && __float_as_uint(hv) >= win_key;
-                    }
-                }
-            }
+            if (sample) hit = k1_sample(k, d, x, valid, u * 64 + lane, k.windowed, hv);
         }
-        const uint64_t hb = __ballot(hit);
-        if (hb) {   // wave-uniform and rare (~3 ks of the S samples): one atomic per wave
-            const int leader = __ffsll((unsigned long long)hb) - 1;
-            uint32_t base = 0;
-            if (lane == leader) base = atomicAdd(win_cnt, (uint32_t)__popcll(hb));
-            base = __shfl(base, leader);
-            const uint32_t pos = base + (uint32_t)__popcll(hb & ((1ull << lane) - 1));
-            if (hit && pos < (uint64_t)d.win_cap) win[pos] = hv;
-            if (hit) atomicAdd(&whist[win_bin(__float_as_uint(hv), win_key)], 1u);   // (no return value)
-        }
-        list_append(ge_mask(x, valid, tl), x, u * 256, c, lo, lv, seg);
+        k1_window_append(k, d.win_cap, hit, hv, lane);
+        list_append(ge_mask(x, valid, k.tl), x, u * 256, c, w.lst_off, w.lst_val, seg);
         mk = max(mk, tile_max_key(x, valid));
     }
-    mk = wave_max(mk);
-    if (lane == 0 && live) {
-        const bool tail = d.tail && ls == d.nseg - 1;   // its scalar tail is compensated outside K1
-        w.seg_lcnt[seg] = tail ? lcnt_pack(kCap + 1, 0xFFFFu) : lcnt_pack(c, lmax_code(mk));
-        // one atomic per wave with a spilled segment (c is wave-uniform; shard by block)
-        if (c > (uint32_t)kCap) atomicAdd(&w.st[t].spill[epoch & 1][blockIdx.x % kSpillShards], 1u);
-    }
+    // (the segment with the scalar tail, compensated outside K1, is marked spilled)
+    k1_segment_end(c, mk, lane == 0 && live, d.tail && ls == d.nseg - 1, w.seg_lcnt + seg, w.st[t].spill[epoch & 1]);
 }
 
 __global__ void k_no_lists(SelWS w) {

@@ -1,10 +1,11 @@
 // Selection, K1 for 16-bit state (bf16 / fp16): k_compensate_list16, the flat bucket's
-// one-tensor K1 over 16-bit momentum / velocity / gradient. k_compensate16's arithmetic
-// (half.hip: each of the reference's ops in fp32, rounded to the dtype) with everything
-// k_compensate_list (select_k1.hpp) fuses: the strided sample, the sample window and the
-// speculative candidate lists, all taken from the new velocity's exact fp32 image, which
-// it also writes. After it the segment state is what k_compensate_list would have left
-// had it run on the image, so dgc_compress_finish serves the image unchanged.
+// one-tensor K1 over 16-bit momentum / velocity / gradient. Its own: how a tile is loaded,
+// compensated (k_compensate16's arithmetic, half.hip: each of the reference's ops in fp32,
+// rounded to the dtype) and stored, and the new velocity's exact fp32 image, which it
+// writes. The strided sample, the sample window, the candidate lists and the segment's end
+// are taken from that image by select_k1.hpp's shared steps (k1_segment_begin, k1_sample,
+// k1_window_append, k1_segment_end), the ones k_compensate_list runs, so
+// dgc_compress_finish serves the image unchanged.
 //
 // Layout: the fp32 kernel's. One wave per segment, element group (4 elements) index =
 // 256*seg + 64*u + lane (u = 0..3): an 8-B load per lane and array, 512 B contiguous per
@@ -96,8 +97,8 @@ k_compensate_list16(const uint16_t* __restrict__ g16, uint16_t* __restrict__ mmt
     const TDesc d = ot.d;   // by value: stores below cannot alias it
     const int lane = threadIdx.x & 63, wave = wave_id();
     const int64_t ls = (int64_t)blockIdx.x * kSegPerBlock4 + wave;   // local segment
-    // a wave past the last segment loads nothing and lists nothing (no early exit, as in
-    // k_compensate_list)
+    // a wave past the last segment loads nothing and lists nothing (no early exit: a
+    // branch here would split the state reads from the streaming loads)
     const bool live = ls < d.nseg;
     const bool first = blockIdx.x == 0 && threadIdx.x == 0;
     const bool sample = d.samp_off >= 0;
@@ -145,37 +146,19 @@ k_compensate_list16(const uint16_t* __restrict__ g16, uint16_t* __restrict__ mmt
         }
         w.small[0] = 0;
     }
-    const float tl = w.spec ? spec0 : __builtin_huge_valf();
-    if (first) st->t_list = tl;
     if (!sample) start = 0;
     const int64_t scount = !sample ? 0 : ceil_div(d.n - start, d.stride);
-    if (first) {
-        w.starts[0] = start;
-        w.scnt[0] = sample ? scount : d.n;
-    }
-    float* sout = sample ? w.samples + d.samp_off : nullptr;
-    // the sample window list, as in k_compensate_list
-    float* win = w.samples + d.win_off;
-    const float tw = w.spec ? spec2 : __builtin_huge_valf();
-    const uint32_t win_key = abs_key(tw < __builtin_huge_valf() ? tw : tl);
-    const bool windowed = sample && d.win_cap > 0;
-    uint32_t* win_cnt = &w.st[0].win_cnt[epoch & 1];
-    uint32_t* whist = reinterpret_cast<uint32_t*>(w.samples + d.whist_off);
-    if (windowed && first) st->win_key = win_key;
-    int64_t q0 = 0, r0 = 0;
-    if (sample) floor_divmod_fast(ls * kSeg - start, d.stride, d.inv_stride, q0, r0);
+    const K1Seg k = k1_segment_begin(w, d, 0, st, first, true, spec0, spec2, epoch, ls, start, scount);
     uint32_t c = 0, mk = 0;
     const int64_t seg = d.seg0 + ls;
-    uint16_t* lo = w.lst_off;
-    float* lv = w.lst_val;
 #pragma unroll
     for (int u = 0; u < kSegTiles; ++u) {
         const int64_t e = 4 * (seg4 + u * 64 + lane);
         // elements of the group inside the tensor
         const uint32_t valid =
             !live ? 0u : (e + 3 < n ? 0xFu : (e + 2 < n ? 7u : (e + 1 < n ? 3u : (e < n ? 1u : 0u))));
-        // a partial group is compensated and sampled, but not listed or windowed
-        // (k_compensate_list leaves it to the scalar tail)
+        // a partial group is compensated and sampled, but not listed or windowed: its
+        // segment is marked spilled (d.tail)
         const uint32_t lvalid = valid == 0xFu ? 0xFu : 0u;
         float x[4] = {0.f, 0.f, 0.f, 0.f};
         bool hit = false;   // this lane's sample (at most one per group: stride >= 4) joins the window
@@ -194,41 +177,12 @@ k_compensate_list16(const uint16_t* __restrict__ g16, uint16_t* __restrict__ mmt
             st_nt(mmt + u * 64 + lane, pack4<DT>(mx));
             st_nt(vec + u * 64 + lane, pack4<DT>(x));
             st_stream(im + u * 64 + lane, make_float4(x[0], x[1], x[2], x[3]), wt);
-            if (sample) {
-                const uint32_t tt = (uint32_t)r0 + 4u * (uint32_t)(u * 64 + lane);
-                const uint32_t s32 = (uint32_t)d.stride;
-                uint32_t q1, r;
-                divmod_u32(tt, s32, d.inv_stride_f, q1, r);
-                const uint32_t j = r == 0 ? 0u : s32 - r;
-                if (j < 4 && ((valid >> j) & 1u)) {
-                    const int64_t qi = q0 + q1 + (r == 0 ? 0 : 1);
-                    if (qi >= 0 && qi < scount) {
-                        hv = fabsf(x[j]);
-                        sout[qi] = hv;
-                        hit = windowed && lvalid && __float_as_uint(hv) >= win_key;
-                    }
-                }
-            }
+            if (sample) hit = k1_sample(k, d, x, valid, u * 64 + lane, k.windowed && lvalid, hv);
         }
-        const uint64_t hb = __ballot(hit);
-        if (hb) {   // wave-uniform and rare: one atomic per wave
-            const int leader = __ffsll((unsigned long long)hb) - 1;
-            uint32_t base = 0;
-            if (lane == leader) base = atomicAdd(win_cnt, (uint32_t)__popcll(hb));
-            base = __shfl(base, leader);
-            const uint32_t pos = base + (uint32_t)__popcll(hb & ((1ull << lane) - 1));
-            if (hit && pos < (uint64_t)d.win_cap) win[pos] = hv;
-            if (hit) atomicAdd(&whist[win_bin(__float_as_uint(hv), win_key)], 1u);   // (no return value)
-        }
-        list_append(ge_mask(x, lvalid, tl), x, u * 256, c, lo, lv, seg);
+        k1_window_append(k, d.win_cap, hit, hv, lane);
+        list_append(ge_mask(x, lvalid, k.tl), x, u * 256, c, w.lst_off, w.lst_val, seg);
         mk = max(mk, tile_max_key(x, lvalid));
     }
-    mk = wave_max(mk);
-    if (lane == 0 && live) {
-        const bool tail = d.tail && ls == d.nseg - 1;   // marked as the fp32 K1 marks it
-        w.seg_lcnt[seg] = tail ? lcnt_pack(kCap + 1, 0xFFFFu) : lcnt_pack(c, lmax_code(mk));
-        // one atomic per wave with a spilled segment (c is wave-uniform; shard by block)
-        if (c > (uint32_t)kCap) atomicAdd(&w.st[0].spill[epoch & 1][blockIdx.x % kSpillShards], 1u);
-    }
+    k1_segment_end(c, mk, lane == 0 && live, d.tail && ls == d.nseg - 1, w.seg_lcnt + seg, w.st[0].spill[epoch & 1]);
 }
 }  // namespace dgc

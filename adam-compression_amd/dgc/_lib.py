@@ -374,6 +374,21 @@ def require_cuda_float(t, what, contiguous=True):
     return t.dtype
 
 
+def require_out(out, dtype, numel, device, what, name="out"):
+    """A decompress output of an engine: contiguous, of the parameters' dtype, exactly
+    ``numel`` elements, on the engine's device."""
+    if require_cuda_float(out, what) != dtype or out.numel() != numel or out.device != device:
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} tensor of {numel} elements on {device} "
+                         f"(got {out.dtype} [{out.numel()}] on {out.device})")
+
+
+def mask_packed16(payload, capacity, vdtype, idtype, mmt, vec, numel, device):
+    """DGCSGDMemory.update on 16-bit state from the packed payload (``dgc_mask_packed16``):
+    the payload's indices zeroed in ``vec`` and, unless None, in ``mmt``."""
+    check(lib().dgc_mask_packed16(payload.data_ptr(), capacity, VD[vdtype], ID[idtype], ptr(mmt), vec.data_ptr(), numel,
+                                  stream_of(device)), "dgc_mask_packed16")
+
+
 def require_cuda_f32(t, what):
     if not (torch.is_tensor(t) and t.is_cuda):
         raise RuntimeError(f"{what}: the DGC hot path runs on the MI355X only (got a "

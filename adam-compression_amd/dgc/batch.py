@@ -144,7 +144,7 @@ class DGCBatch(ReceiveSide):
         # a new layout: a new receive side (payload / gather buffers, exchange, decompress
         # workspace bound to ``status``), which remembers nothing of the previous step
         self.rx = Receiver(self.capacity, self.flat_numel, self.world, self.vdtype, self.idtype, self.device,
-                           self.status, self._fill, self.exchange_parts, self.payload_extra, self.half,
+                           self.status, self._fill, self.exchange_parts, self.payload_extra, self.dtype,
                            unsent="DGCBatch: decompress of a split exchange before send() / exchange()")
 
     def flush(self):
@@ -250,10 +250,9 @@ class DGCBatch(ReceiveSide):
             _lib.check(L.dgc_batch_select(ctypes.byref(self.desc), self._vec32.data_ptr(), None, self._starts_arr,
                                           self.payload.data_ptr(), self.info.data_ptr(), self.ws.data_ptr(),
                                           self.ws.numel(), _lib.SYNC_DEVICE, st), "dgc_batch_select")
-            _lib.check(L.dgc_mask_packed16(self.payload.data_ptr(), self.capacity, _lib.VD[self.vdtype],
-                                           _lib.ID[self.idtype],
-                                           self._mmt_flat.data_ptr() if self.momentum_masking else None,
-                                           self._vec_flat.data_ptr(), self.flat_numel, st), "dgc_mask_packed16")
+            _lib.mask_packed16(self.payload, self.capacity, self.vdtype, self.idtype,
+                               self._mmt_flat if self.momentum_masking else None, self._vec_flat, self.flat_numel,
+                               self.device)
             return
         _lib.check(self._L.dgc_batch_compress_finish(ctypes.byref(self.desc), self._mmt_flat.data_ptr(),
                                                      self._vec_flat.data_ptr(), self.payload.data_ptr(),
@@ -281,19 +280,9 @@ class DGCBatch(ReceiveSide):
         rewritten by every backward), only the previous step's gathered indices are
         re-zeroed instead of the whole buffer (``Receiver``, dgc/exchange.py)."""
         out = self.out_flat if out_flat is None else out_flat
-        if _lib.require_cuda_float(out, "DGCBatch.decompress") != self.dtype or out.numel() != self.flat_numel \
-                or out.device != self.device:
-            raise ValueError(f"DGCBatch.decompress: out_flat must be a contiguous {self.dtype} tensor of "
-                             f"{self.flat_numel} elements on {self.device} (got {out.dtype} [{out.numel()}] on "
-                             f"{out.device})")
-        if self.half:   # zero_(), the runs in rank order (each add rounded), the 1/W scale
-            self.rx.wait()
-            _lib.check(self._L.dgc_decompress_packed16(
-                self.gathered.data_ptr(), self.world, self.rank_stride, self.capacity, _lib.VD[self.vdtype],
-                _lib.ID[self.idtype], out.data_ptr(), _lib.VD[self.dtype], self.flat_numel, 1.0 / self.world,
-                ctypes.c_void_p(self.status.decompress_words), _lib.stream_of(self.device)), "dgc_decompress_packed16")
-        else:
-            self.rx.decompress(out, out.untyped_storage().data_ptr() == self.grad_flat.untyped_storage().data_ptr())
+        _lib.require_out(out, self.dtype, self.flat_numel, self.device, "DGCBatch.decompress", "out_flat")
+        # (16-bit: zero_(), the runs in rank order, each add rounded, the 1/W scale: HalfExchange)
+        self.rx.decompress(out, out.untyped_storage().data_ptr() == self.grad_flat.untyped_storage().data_ptr())
         return out
 
     def step(self, starts=None):

@@ -131,7 +131,7 @@ class DGCBucket(ReceiveSide):
         self.info = torch.zeros(_lib.INFO_BYTES, dtype=torch.uint8, device=dev)
         # the payload and gather buffers, the exchange and the decompress (dgc/exchange.py)
         self.rx = Receiver(self.k, N, self.world, self.vdtype, self.idtype, dev, self.status, fill, exchange_parts,
-                           half=self.half, unsent="DGCBucket: decompress of a split exchange before exchange()")
+                           dtype=dtype, unsent="DGCBucket: decompress of a split exchange before exchange()")
         self._L = L
         if self.fill in ("allgather", "sparse"):
             self.side = torch.cuda.Stream(device=dev)
@@ -199,9 +199,8 @@ class DGCBucket(ReceiveSide):
                                              base + self.voff, base + self.ioff, base, self.info.data_ptr(),
                                              self.ws.data_ptr(), self.ws.numel(), _lib.SYNC_DEVICE, st),
                        "dgc_compress_finish")
-            _lib.check(L.dgc_mask_packed16(base, self.k, _lib.VD[self.vdtype], _lib.ID[self.idtype],
-                                           self._mmt.data_ptr() if self.momentum_masking else None,
-                                           self._vec.data_ptr(), self.numel, st), "dgc_mask_packed16")
+            _lib.mask_packed16(self.payload, self.k, self.vdtype, self.idtype,
+                               self._mmt if self.momentum_masking else None, self._vec, self.numel, self.device)
             return
         self._pending = self.params.update_memory == 2
         _lib.check(L.dgc_compress_finish(self._vec.data_ptr(), self._mmt.data_ptr(), self.start, self.stride,
@@ -210,30 +209,19 @@ class DGCBucket(ReceiveSide):
                                          self.info.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
                                          _lib.SYNC_DEVICE, _lib.stream_of(self.device)), "dgc_compress_finish")
 
-    def decompress(self, out, dense=True):
+    def decompress(self, out, dense=True, aliased=False):
         """dense: out = scale * (rank-order sum of the gathered entries), zeros elsewhere.
         dense=False: out already holds +0.0 (see ``Receiver.zero``); only the entries are
         written. fill="sparse": a dense decompress into the previous step's untouched
         output re-zeroes only the previous entries (see ``Receiver``). A 16-bit bucket:
-        zero_(), the runs in rank order (each add rounded to the dtype), the 1/W scale."""
-        if self.half:
-            if not dense:
-                raise NotImplementedError(f"DGCBucket.decompress: dense=False on {self.dtype} parameters")
-            if _lib.require_cuda_float(out, "DGCBucket.decompress") != self.dtype or out.numel() != self.numel \
-                    or out.device != self.device:
-                raise ValueError(f"DGCBucket.decompress: out must be a contiguous {self.dtype} tensor of "
-                                 f"{self.numel} elements on {self.device} (got {out.dtype} [{out.numel()}] on "
-                                 f"{out.device})")
-            self.rx.wait()
-            _lib.check(self._L.dgc_decompress_packed16(
-                self.gathered.data_ptr(), self.world, self.rank_stride, self.k, _lib.VD[self.vdtype],
-                _lib.ID[self.idtype], out.data_ptr(), _lib.VD[self.dtype], self.numel, 1.0 / self.world,
-                ctypes.c_void_p(self.status.decompress_words), _lib.stream_of(self.device)), "dgc_decompress_packed16")
-            return
-        if dense:
-            self.rx.decompress(out)
-        else:
+        zero_(), the runs in rank order (each add rounded to the dtype), the 1/W scale,
+        always dense (``HalfExchange``); its ``out`` is checked. ``aliased``: see ``step``."""
+        if not dense:
             self.rx.scatter(out)
+            return
+        if self.half:
+            _lib.require_out(out, self.dtype, self.numel, self.device, "DGCBucket.decompress")
+        self.rx.decompress(out, aliased)
 
     def _zero_on_side(self, out, sparse):
         """zero_() of the output on the side stream. sparse: the re-zero of the previous
@@ -264,13 +252,11 @@ class DGCBucket(ReceiveSide):
             self._zero_on_side(out, True)
 
         def decompress():
-            if self.half:   # always the dense 16-bit decompress
-                self.decompress(out)
-            elif cleared or self.fill == "allgather":   # the entries onto the re-zeroed / filled output
+            if cleared or self.fill == "allgather":   # the entries onto the re-zeroed / filled output
                 torch.cuda.current_stream(self.device).wait_event(self._ev_filled)
                 self.rx.scatter(out, cleared)
-            else:
-                self.rx.decompress(out, aliased)
+            else:   # (16-bit: always)
+                self.decompress(out, aliased=aliased)
 
         for name, fn in (("compensate", lambda: self.compensate(grad)), ("select", self.select),
                          ("allgather", self.exchange), ("decompress", decompress)):

@@ -14,7 +14,8 @@ decompress's bit for bit (same rank-order sums; tests/test_gpu_split.py).
 
 Used by DGCBucket / DGCBatch (fp32 parameters) at W > 1, through the ``Receiver`` both
 engines share: the back half of a step — packed payload -> allgather (``SingleExchange``
-or ``SplitExchange``) -> zero_() or sparse re-zero -> scatter; ``parts="auto"`` splits a
+or ``SplitExchange``; ``HalfExchange``, always one allgather, for 16-bit parameters) ->
+zero_() or sparse re-zero -> scatter; ``parts="auto"`` splits a
 step of >= 2^21 gathered entries (2 parts at W <= 4, 4 at W = 8) and leaves smaller ones
 to one allgather: each extra collective costs ~35 us of fixed hand-off
 and hides at most its share of the scatter, which at 2M entries (flat-1B, W = 2: 0.07
@@ -30,7 +31,7 @@ import torch
 
 from . import _lib, comm
 
-__all__ = ["Receiver", "ReceiveSide", "ReuseMemory", "SingleExchange", "SplitExchange", "split_parts"]
+__all__ = ["HalfExchange", "Receiver", "ReceiveSide", "ReuseMemory", "SingleExchange", "SplitExchange", "split_parts"]
 
 
 def split_parts(world, capacity, parts="auto"):
@@ -70,7 +71,7 @@ def agree(parts):
 
 
 class _Exchange:
-    """What the two exchanges share. Both offer ``send(payload, gathered)`` -> handles,
+    """What the exchanges share. All offer ``send(payload, gathered)`` -> handles,
     ``clear(prev_gathered, out, stream)``, ``scatter(gathered, handles, out, scale,
     cleared)`` (the entries onto an ``out`` that holds +0.0) and ``decompress`` (zero_()
     + scatter); ``streamed``: the handles are waited for one by one by the scatter."""
@@ -128,6 +129,33 @@ class SingleExchange(_Exchange):
             self._run("dgc_decompress_packed", [gathered], handles, out, scale)
         else:
             self._run("dgc_decompress_packed_over", [gathered, prev], handles, out, scale)
+
+
+class HalfExchange(_Exchange):
+    """One allgather of the whole payload and the 16-bit packed decompress (bf16 / fp16
+    parameters): zero_(), the runs in rank order (each add rounded to the dtype) and the
+    1/W scale in one call, always dense. It has no workspace; its error bits go straight
+    to ``status``, whose name (the engine's) its refusals carry."""
+    parts, streamed = 1, False
+    send = SingleExchange.send
+
+    def __init__(self, capacity, numel, world, rank_stride, vdtype, idtype, dtype, device, status):
+        self._L, self.numel, self.device, self.dtype, self.status = _lib.lib(), int(numel), device, dtype, status
+        self._layout = (world, rank_stride, capacity, _lib.VD[vdtype], _lib.ID[idtype])
+
+    def decompress(self, gathered, handles, out, scale, prev):
+        for h in handles:
+            h.wait()
+        _lib.check(self._L.dgc_decompress_packed16(
+            gathered.data_ptr(), *self._layout, out.data_ptr(), _lib.VD[self.dtype], self.numel, scale,
+            ctypes.c_void_p(self.status.decompress_words), _lib.stream_of(self.device)), "dgc_decompress_packed16")
+
+    def scatter(self, gathered, handles, out, scale, cleared):
+        raise NotImplementedError(f"{self.status.what}.decompress: dense=False on {self.dtype} parameters")
+
+    def clear(self, prev_gathered, out, stream):
+        raise NotImplementedError(f"{self.status.what}: fill='sparse' on {self.dtype} parameters (the 16-bit "
+                                  "decompress is the dense fill with the scatter)")
 
 
 class SplitExchange(_Exchange):
@@ -210,6 +238,9 @@ class Receiver(ReuseMemory):
     ``parts`` of them; none at W = 1, where the gather buffers are the payload buffers)
     -> ``grad.zero_()`` (dgc/compression.py:191) -> the scatter of the gathered entries.
 
+    ``dtype``: the parameters'. bf16 / fp16 take ``HalfExchange``: one part, always the
+    dense 16-bit decompress, no fp32 decompress workspace (``dec_ws`` is None).
+
     ``fill``: how the zero_() is done. ``"inline"`` (``"auto"``, and always for 16-bit
     parameters) is a dense fill with the scatter. ``"sparse"`` (opt-in) treats ``out``
     as a persistent output: when it is the tensor the previous step decompressed into,
@@ -226,9 +257,10 @@ class Receiver(ReuseMemory):
     next step); ``unsent`` is the error of a split decompress before its exchange."""
 
     def __init__(self, capacity, numel, world, vdtype, idtype, device, status, fill="auto", exchange_parts="auto",
-                 payload_extra=0, half=False, unsent="decompress of a split exchange before send()"):
+                 payload_extra=0, dtype=torch.float32, unsent="decompress of a split exchange before send()"):
         self.capacity, self.numel, self.world = int(capacity), int(numel), int(world)
         self.scale, self.unsent = 1.0 / self.world, unsent
+        half = dtype in _lib.HALF   # the parameters' dtype: 16-bit takes HalfExchange
         # the dense zero_() is always right; the re-zero is opt-in (fp32)
         self.fill = "inline" if fill == "auto" or half else fill
         self.rank_stride, self.voff, self.ioff = _lib.payload_layout(self.capacity, vdtype, idtype)
@@ -249,10 +281,14 @@ class Receiver(ReuseMemory):
         else:
             self.gathers = ([torch.zeros(self.world * self.rank_stride, dtype=torch.uint8, device=device)
                              for _ in range(nbuf)] if self.exchanging else self.payloads)
-            self.xchg = SingleExchange(self.capacity, self.numel, self.world, self.rank_stride, vdtype, idtype, device)
-        # what other files read: the split exchange or None, the single one's workspace or None
-        self.split, self.dec_ws = (self.xchg, None) if self.parts > 1 else (None, self.xchg.ws)
-        status.bind(self.xchg.ws)
+            self.xchg = (HalfExchange(self.capacity, self.numel, self.world, self.rank_stride, vdtype, idtype, dtype,
+                                      device, status) if half else
+                         SingleExchange(self.capacity, self.numel, self.world, self.rank_stride, vdtype, idtype, device))
+        # what other files read: the split exchange or None, the fp32 single one's workspace or None
+        self.split = self.xchg if self.parts > 1 else None
+        self.dec_ws = None if half or self.parts > 1 else self.xchg.ws
+        if not half:   # (the 16-bit decompress writes status's words itself)
+            status.bind(self.xchg.ws)
         self._par, self._inflight = 0, []
 
     def begin(self):

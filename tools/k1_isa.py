@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""What the compiler made of K1 (k_compensate_list) and of the plain compensate kernels.
+"""What the compiler made of K1 (k_compensate_list), of K1-16 (k_compensate_list16) and of
+the plain compensate kernels.
 
 Host only, no GPU: compiles a .hip file of adam-compression_amd/csrc to gfx950 assembly
 with the Makefile's flags (read from the Makefile) and prints, per kernel instantiation,
@@ -12,7 +13,8 @@ with the Makefile's flags (read from the Makefile) and prints, per kernel instan
   flat                   flat_ loads in the kernel's text (a load whose address space the
                          compiler could not prove)
   walks                  the walks through the kernel that the figures below range over (+: cut off)
-  stream                 16-B non-temporal loads on a walk (K1: a wave's 12)
+  stream                 non-temporal streaming loads on a walk, a wave's 12: 16-B ones in K1,
+                         8-B ones in K1-16
   before-vm-wait         how many of them are issued before the first wait on the vector
                          memory counter that waits for one of them
   waits-before / mem     waits in front of the first streaming load / those of them that
@@ -28,6 +30,11 @@ without a warning:
   - a streaming load is any (global|flat)_load_dwordx4 whose operands include `nt`; another
     16-B non-temporal load in the kernel (none today) would be counted as one, and a
     streaming load the compiler emitted without `nt`, or split into narrower loads, would not;
+  - K1-16's streaming load is any (global|flat)_load_dwordx2 with `nt`. The 8-B form is also
+    what a plain 64-bit read compiles to (a pointer, an int64 table entry): one that carried
+    `nt` would be counted, and two streaming loads of a lane that the compiler merged into one
+    dwordx4 would not. The gradient's partial last group (ld_tail16) is 2-B loads without
+    `nt`, so counts as `mem`, never as a streaming load;
   - a vmcnt wait that finds nothing outstanding on the walk is taken for the wait of a loop
     whose load stands below it in the text (task_first's search) and counted as
     memory-dependent; a redundant wait would be counted the same way;
@@ -37,7 +44,7 @@ without a warning:
   - loads and stores retire in issue order on their counter (true of gfx9 vector memory;
     scalar loads are only ever waited for with lgkmcnt(0) here).
 
-  tools/k1_isa.py                      # K1's twelve instantiations, as a markdown table
+  tools/k1_isa.py                      # K1's twelve instantiations and K1-16's four, as a markdown table
   tools/k1_isa.py --compensate         # k_compensate4 / k_compensate_mt (compensate.hip)
   tools/k1_isa.py --asm FILE.s         # read an assembly file instead of compiling
   tools/k1_isa.py --trace 'ILb1ELb1ELi0E'   # the memory operations and waits of one kernel
@@ -49,7 +56,7 @@ import subprocess
 import sys
 import tempfile
 
-kSegLoads = 12   # a wave's 16-B streaming loads (three arrays x kSegTiles)
+kSegLoads = 12   # a wave's streaming loads (three arrays x kSegTiles)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "adam-compression_amd", "csrc")
 
@@ -111,7 +118,8 @@ def regs(op):
 class Path:
     """One walk through a kernel: what is outstanding, and what it has counted."""
 
-    def __init__(self):
+    def __init__(self, stream_op="dwordx4"):
+        self.stream_op = stream_op   # the width of the kernel's streaming load
         self.pc = 0
         self.karg = {0, 1}     # SGPRs that hold the kernel-argument pointer or an offset copy of it
         self.vm = []           # outstanding vector memory operations, oldest first: 'mem' | 'stream' | 'store'
@@ -142,7 +150,7 @@ class Path:
         elif re.match(r"^(global|flat|buffer|scratch)_load", op):
             if op.startswith("flat_"):
                 self.lgkm.append("mem")
-            if re.match(r"^(global|flat)_load_dwordx4$", op) and "nt" in args:
+            if re.match(r"^(global|flat)_load_%s$" % self.stream_op, op) and "nt" in args:
                 self.stream += 1
                 self.mem_to_last += self.mem_pending
                 self.mem_pending = 0
@@ -189,7 +197,7 @@ class Path:
                 self.karg -= dst
 
 
-def scan(body, nstream=None, max_paths=20000):
+def scan(body, nstream=None, max_paths=20000, stream_op="dwordx4"):
     """Every walk through the kernel up to its nstream-th streaming load (None: to its end).
 
     All lanes are taken as active: a branch on an empty exec mask is not taken, one on a
@@ -204,7 +212,7 @@ def scan(body, nstream=None, max_paths=20000):
             label[m.group(1)] = len(prog)
         elif ins and not ins.startswith("."):
             prog.append(ins)
-    done, todo, seen = [], [Path()], set()
+    done, todo, seen = [], [Path(stream_op)], set()
     while todo and len(done) + len(todo) < max_paths:
         p = todo.pop()
         while True:
@@ -257,6 +265,9 @@ def pretty(name):
     m = re.search(r"k_compensate_listILb(\d)ELb(\d)ELi(\d)E", name)
     if m:
         return "K1 NEST=%s ONE=%s CLIP=%s" % m.groups()
+    m = re.search(r"k_compensate_list16ILi(\d)ELb(\d)E", name)
+    if m:
+        return "K1-16 DT=%s NEST=%s" % m.groups()
     m = re.search(r"\d+(k_compensate\w*?)I(\w+?)EEv", name)
     return "%s<%s>" % m.groups() if m else name
 
@@ -267,7 +278,7 @@ def main():
     ap.add_argument("--compensate", action="store_true", help="compensate.hip's k_compensate4 / k_compensate_mt")
     ap.add_argument("--trace", metavar="REGEX", help="print the memory operations and waits of the kernels matching it")
     a = ap.parse_args()
-    src, name_re = ("compensate.hip", r"k_compensate(4|_mt)I") if a.compensate else ("select.hip", r"k_compensate_listI")
+    src, name_re = ("compensate.hip", r"k_compensate(4|_mt)I") if a.compensate else ("select.hip", r"k_compensate_list(16)?I")
     text = open(a.asm).read() if a.asm else compile_asm(src)
     print("| kernel | vgpr | occ | launched | scratch | flat | walks | stream | before-vm-wait | waits-before / mem | mem-to-last |")
     print("|---|---|---|---|---|---|---|---|---|---|---|")
@@ -277,7 +288,9 @@ def main():
         occ = trailer(tr, "Occupancy")
         one = re.search(r"k_compensate_listILb\dELb1E", name)
         launched = "%d" % occ if not (cap and one) else "%d / %d" % (min(occ, cap), occ)
-        walks, cut = scan(body, nstream=None if a.compensate else kSegLoads)
+        # K1-16 streams 8-B loads and has no LDS-bounded launch (`one` does not match it)
+        walks, cut = scan(body, nstream=None if a.compensate else kSegLoads,
+                          stream_op="dwordx2" if "k_compensate_list16I" in name else "dwordx4")
         if a.trace:
             if re.search(a.trace, name) and walks:
                 for what, w in (("fewest", min(walks, key=lambda w: w.mem_to_last)), ("most", max(walks, key=lambda w: w.mem_to_last))):
