@@ -24,15 +24,19 @@ constexpr int kStatChunk = kBlock * kStatPerLane;   // elements per partial
 constexpr int kClipMax = 64;                        // tensors per launch (table in the arguments)
 constexpr int kClipPerThread = 4;
 
-struct ClipChunk {
+template <typename T>
+struct ClipChunkT {
     int32_t count, first;                // tensors [first, first + count) of the call
     int32_t bstart[kClipMax + 1];        // first workgroup of each tensor (prefix)
-    float* src[kClipMax];
+    T* src[kClipMax];
     int64_t n[kClipMax];
     int64_t poff[kClipMax];              // stats: the tensor's first partial
 };
+using ClipChunk = ClipChunkT<float>;
+using ClipChunk16 = ClipChunkT<const uint16_t>;   // K0-16: bf16 / fp16 sources
 
-__device__ __forceinline__ int chunk_tensor(const ClipChunk& c, int b) {
+template <typename C>
+__device__ __forceinline__ int chunk_tensor(const C& c, int b) {
     int lo = 0, hi = c.count - 1;        // bstart[t] <= b < bstart[t + 1]
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -95,9 +99,60 @@ __global__ void __launch_bounds__(kBlock) k_stat_partial(ClipChunk c, double* __
     if (threadIdx.x == 0) part[c.poff[t] + j] = acc;
 }
 
-template <bool MAX>
+// K0-16: the same partials from a bf16 / fp16 source. Element e keeps its partial, lane and
+// position, so the fp64 sum is the one k_stat_partial forms on the widened tensor. A lane's
+// four groups are 8-B non-temporal loads (the width K1-16 streams), all issued before the
+// first is used; a source that is not 8-B aligned, and the group the tensor ends in, take
+// the same elements by 2-B loads, none past numel. (One 8-KB partial per workgroup: at 1e9
+// elements the pass takes 0.57 ms, about K0's time per ELEMENT (0.65 ms), so it is not the
+// bytes that bound it; two partials per workgroup with all eight loads in flight measured
+// 0.64 ms and was not kept. DESIGN.md §4 "Gradient clipping".)
+typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+
+template <int DT, bool MAX>
+__global__ void __launch_bounds__(kBlock) k_stat_partial16(ClipChunk16 c, double* __restrict__ part) {
+    const int b = (int)blockIdx.x;
+    const int t = chunk_tensor(c, b);
+    DGC_GLB const uint16_t* src = glb(c.src[t]);
+    const int64_t n = c.n[t];
+    const int64_t j = b - c.bstart[t];
+    const bool vec = (reinterpret_cast<uintptr_t>(c.src[t]) & 7u) == 0;
+    uint32_t lo[kStatPerLane / 4], hi[kStatPerLane / 4];
+#pragma unroll
+    for (int u = 0; u < kStatPerLane / 4; ++u) {
+        const int64_t e = j * kStatChunk + (int64_t)u * (kBlock * 4) + 4 * (int64_t)threadIdx.x;
+        lo[u] = hi[u] = 0u;   // past the end: +0
+        if (vec && e + 3 < n) {
+            const u2v v = __builtin_nontemporal_load(reinterpret_cast<DGC_GLB const u2v*>(src + e));
+            lo[u] = v[0], hi[u] = v[1];
+        } else {
+            if (e < n) lo[u] = (uint32_t)src[e];
+            if (e + 1 < n) lo[u] |= (uint32_t)src[e + 1] << 16;
+            if (e + 2 < n) hi[u] = (uint32_t)src[e + 2];
+            if (e + 3 < n) hi[u] |= (uint32_t)src[e + 3] << 16;
+        }
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int u = 0; u < kStatPerLane / 4; ++u) {
+        const uint16_t h[4] = {(uint16_t)(lo[u] & 0xFFFFu), (uint16_t)(lo[u] >> 16), (uint16_t)(hi[u] & 0xFFFFu),
+                               (uint16_t)(hi[u] >> 16)};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float y = h16_to_f32<DT>(h[q]);
+            if (MAX) acc = (double)nan_max((float)acc, fabsf(y));
+            else acc += (double)y * (double)y;
+        }
+    }
+    acc = block_fold<MAX>(acc);
+    if (threadIdx.x == 0) part[c.poff[t] + j] = acc;
+}
+
+// RDT: the result rounded to fp32, then (a 16-bit source, K0-16) to that dtype, and stored
+// as the fp32 image of the dtype's value: what an ATen reduction leaves in a 0-dim tensor.
+template <bool MAX, int RDT = DGC_F32, typename C = ClipChunk>
 __global__ void __launch_bounds__(kBlock)
-k_stat_final(ClipChunk c, const double* __restrict__ part, float* __restrict__ stats, int root) {
+k_stat_final(C c, const double* __restrict__ part, float* __restrict__ stats, int root) {
     const int t = (int)blockIdx.x;
     const int64_t np = ceil_div(c.n[t], (int64_t)kStatChunk);
     const double* __restrict__ p = part + c.poff[t];
@@ -118,20 +173,25 @@ k_stat_final(ClipChunk c, const double* __restrict__ part, float* __restrict__ s
         }
     }
     acc = block_fold<MAX>(acc);
-    if (threadIdx.x == 0) stats[c.first + t] = (float)(root ? sqrt(acc) : acc);
+    if (threadIdx.x == 0) {
+        const float r = (float)(root ? sqrt(acc) : acc);
+        stats[c.first + t] = RDT == DGC_F32 ? r : round16<RDT == DGC_F32 ? DGC_BF16 : RDT>(r);
+    }
 }
 
-static int clip_chunk(float* const* srcs, const int64_t* numels, int32_t t0, int32_t total, int64_t per_block,
-                      ClipChunk& c, int64_t& blocks, const char* who) {
-    c = ClipChunk{};
+template <typename T>
+static int clip_chunk(T* const* srcs, const int64_t* numels, int32_t t0, int32_t total, int64_t per_block,
+                      ClipChunkT<T>& c, int64_t& blocks, const char* who) {
+    constexpr unsigned align = sizeof(T);
+    c = ClipChunkT<T>{};
     c.first = t0;
     c.count = std::min<int32_t>(kClipMax, total - t0);
     blocks = 0;
     for (int i = 0; i < c.count; ++i) {
         const int64_t n = numels[t0 + i];
         if (n < 0 || (n > 0 && !srcs[t0 + i])) DGC_FAIL(DGC_ERR_INVALID, "%s: tensor %d: bad pointer or size", who, t0 + i);
-        if (reinterpret_cast<uintptr_t>(srcs[t0 + i]) & 3u)
-            DGC_FAIL(DGC_ERR_INVALID, "%s: tensor %d is not 4-B aligned", who, t0 + i);
+        if (reinterpret_cast<uintptr_t>(srcs[t0 + i]) & (align - 1))
+            DGC_FAIL(DGC_ERR_INVALID, "%s: tensor %d is not %u-B aligned", who, t0 + i, align);
         c.bstart[i] = (int32_t)blocks;
         c.src[i] = srcs[t0 + i];
         c.n[i] = n;
@@ -225,6 +285,84 @@ int clip_coefs(const float* stats, int32_t count, int32_t mode, float max_norm, 
     return DGC_OK;
 }
 
+// K0-16: the statistic of bf16 / fp16 tensors, as torch leaves it in a 0-dim tensor of the
+// dtype (x.norm(2), x.abs().max()): the fp64 result rounded to fp32, then to the dtype.
+template <int DT>
+static void launch_stats16(bool mx, const ClipChunk16& c, int64_t blocks, double* part, float* stats, hipStream_t st) {
+    const dim3 bd(kBlock), gf((unsigned)c.count);
+    if (blocks > 0) {
+        const dim3 gd((unsigned)blocks);
+        if (mx) hipLaunchKernelGGL((k_stat_partial16<DT, true>), gd, bd, 0, st, c, part);
+        else hipLaunchKernelGGL((k_stat_partial16<DT, false>), gd, bd, 0, st, c, part);
+    }
+    if (mx) hipLaunchKernelGGL((k_stat_final<true, DT, ClipChunk16>), gf, bd, 0, st, c, part, stats, 0);
+    else hipLaunchKernelGGL((k_stat_final<false, DT, ClipChunk16>), gf, bd, 0, st, c, part, stats, 1);   // the 2-norm
+}
+
+int grad_stats16(const void* const* srcs, const int64_t* numels, int32_t count, int32_t kind, int32_t dtype,
+                 float* stats, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (count < 0 || (count > 0 && (!srcs || !numels || !stats)))
+        DGC_FAIL(DGC_ERR_INVALID, "dgc_grad_stats16: null argument");
+    if (kind == DGC_STAT_SUMSQ)
+        DGC_FAIL(DGC_ERR_INVALID, "dgc_grad_stats16: DGC_STAT_SUMSQ (the global variants) is not taken on 16-bit tensors");
+    if (kind != DGC_STAT_NORM2 && kind != DGC_STAT_ABSMAX) DGC_FAIL(DGC_ERR_INVALID, "dgc_grad_stats16: kind %d", (int)kind);
+    if (dtype != DGC_BF16 && dtype != DGC_F16)
+        DGC_FAIL(DGC_ERR_DTYPE, "dgc_grad_stats16: dtype must be DGC_BF16 or DGC_F16 (got %d)", (int)dtype);
+    if (count == 0) return DGC_OK;
+    if (stat_partials(numels, count) < 0) DGC_FAIL(DGC_ERR_INVALID, "dgc_grad_stats16: negative numel");
+    const size_t need = grad_stats_ws(numels, count);
+    if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255))
+        DGC_FAIL(DGC_ERR_WORKSPACE, "dgc_grad_stats16: workspace needs %zu bytes, 256-B aligned", need);
+    // the table's pointers before the first launch (clip_chunk looks at a chunk as it is launched)
+    for (int32_t t = 0; t < count; ++t) {
+        if (numels[t] > 0 && !srcs[t]) DGC_FAIL(DGC_ERR_INVALID, "dgc_grad_stats16: tensor %d: bad pointer or size", t);
+        if (reinterpret_cast<uintptr_t>(srcs[t]) & 1u)
+            DGC_FAIL(DGC_ERR_INVALID, "dgc_grad_stats16: tensor %d is not 2-B aligned", t);
+    }
+    if (stat_partials(numels, count) > 0x7FFFFFFFLL) DGC_FAIL(DGC_ERR_INVALID, "dgc_grad_stats16: too many elements");
+    const uint16_t* const* src16 = reinterpret_cast<const uint16_t* const*>(srcs);   // the ABI's void pointers
+    double* part = static_cast<double*>(ws);
+    int64_t poff = 0;
+    for (int32_t t0 = 0; t0 < count; t0 += kClipMax) {
+        ClipChunk16 c;
+        int64_t blocks;
+        DGC_TRY(clip_chunk(src16, numels, t0, count, kStatChunk, c, blocks, "dgc_grad_stats16"));
+        for (int i = 0; i < c.count; ++i) {
+            c.poff[i] = poff;
+            poff += ceil_div(c.n[i], (int64_t)kStatChunk);
+        }
+        const bool mx = kind == DGC_STAT_ABSMAX;
+        if (dtype == DGC_BF16) launch_stats16<DGC_BF16>(mx, c, blocks, part, stats, st);
+        else launch_stats16<DGC_F16>(mx, c, blocks, part, stats, st);
+        DGC_LAUNCHED();
+    }
+    return DGC_OK;
+}
+
+// `max_norm / (total_norm + 1e-6)` on a 0-dim tensor of a 16-bit dtype: the add, the
+// reciprocal and the product each computed in fp32 and rounded to the dtype.
+template <int DT>
+__global__ void __launch_bounds__(kBlock)
+k_clip_coefs16(const float* stats, int32_t count, float max_norm, float* clip) {
+    const int t = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (t >= count) return;
+    const float total = round16<DT>(__fadd_rn(stats[t], 1e-6f));
+    const float inv = round16<DT>(__fdiv_rn(1.f, total));
+    clip[t] = round16<DT>(__fmul_rn(inv, max_norm));
+}
+
+int clip_coefs16(const float* stats, int32_t count, float max_norm, int32_t dtype, float* clip, hipStream_t st) {
+    if (count < 0 || (count > 0 && (!stats || !clip))) DGC_FAIL(DGC_ERR_INVALID, "dgc_clip_coefs16: null argument");
+    if (dtype != DGC_BF16 && dtype != DGC_F16)
+        DGC_FAIL(DGC_ERR_DTYPE, "dgc_clip_coefs16: dtype must be DGC_BF16 or DGC_F16 (got %d)", (int)dtype);
+    if (count == 0) return DGC_OK;
+    const dim3 gd((unsigned)ceil_div(count, kBlock)), bd(kBlock);
+    if (dtype == DGC_BF16) hipLaunchKernelGGL(k_clip_coefs16<DGC_BF16>, gd, bd, 0, st, stats, count, max_norm, clip);
+    else hipLaunchKernelGGL(k_clip_coefs16<DGC_F16>, gd, bd, 0, st, stats, count, max_norm, clip);
+    DGC_LAUNCHED();
+    return DGC_OK;
+}
+
 template <int CLIP>
 __global__ void __launch_bounds__(kBlock) k_clip_apply(ClipChunk c, ClipArg ca) {
     const int b = (int)blockIdx.x;
@@ -279,4 +417,14 @@ extern "C" int dgc_clip_coefs(const float* stats, int32_t count, int32_t mode, f
 extern "C" int dgc_clip_apply(float* const* tensors, const int64_t* numels, int32_t count, int32_t clip_kind,
                               const float* clip, float clip_value, void* stream) {
     return dgc::clip_apply(tensors, numels, count, clip_kind, clip, clip_value, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int dgc_grad_stats16(const void* const* srcs, const int64_t* numels, int32_t count, int32_t kind,
+                                int32_t dtype, float* stats, void* ws, size_t ws_bytes, void* stream) {
+    return dgc::grad_stats16(srcs, numels, count, kind, dtype, stats, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int dgc_clip_coefs16(const float* stats, int32_t count, float max_norm, int32_t dtype, float* clip,
+                                void* stream) {
+    return dgc::clip_coefs16(stats, count, max_norm, dtype, clip, static_cast<hipStream_t>(stream));
 }

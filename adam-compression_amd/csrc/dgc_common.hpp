@@ -456,6 +456,23 @@ __device__ __forceinline__ float4 clip4(float4 g, float c) {
     if (CLIP == DGC_CLIP_NONE) return g;
     return make_float4(clip1<CLIP>(g.x, c), clip1<CLIP>(g.y, c), clip1<CLIP>(g.z, c), clip1<CLIP>(g.w, c));
 }
+
+// The same clip on an element of a bf16 / fp16 gradient (K1-16; the reference's clip run on
+// a 16-bit tensor): `if coef < 1: x.mul_(coef)` is the fp32 product rounded to the dtype,
+// `x.clamp_(-v, v)` clamps against the bound rounded to the dtype, which leaves a value of
+// the dtype. NaN as clip1. clip_bound16: the call's coefficient from the table entry the
+// kernel loaded (a value of the dtype already, dgc_clip_coefs16) or from the fixed bound.
+template <int DT, int CLIP>
+__device__ __forceinline__ float clip16(float g, float c) {
+    if (CLIP == DGC_CLIP_SCALE) return c < 1.f ? round16<DT>(__fmul_rn(g, c)) : g;
+    return clip1<CLIP>(g, c);
+}
+
+template <int DT, int CLIP>
+__device__ __forceinline__ float clip_bound16(const ClipArg& ca, float tab_entry) {
+    if (CLIP == DGC_CLIP_NONE) return 0.f;
+    return ca.tab ? tab_entry : round16<DT>(ca.value);
+}
 // ---------------------------------------------------------------- error flags
 // A flag the host polls without synchronising (an engine's pinned status sink) or a
 // device int32: every writer stores the same constant — idempotent, so no

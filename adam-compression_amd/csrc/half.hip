@@ -25,42 +25,89 @@
 // 16-bit parameters) runs K1-16 over its flat 16-bit buffers, dgc_batch_select on the
 // image, k_mask_packed16 / k_scatter_packed16 from the packed payloads (their counts
 // read on the device), k_gather16 for the optimizer's p.grad tensors.
+// Local gradient clipping (K0-16, clip.hip: the statistic and the coefficient in the dtype)
+// is a template parameter of k_compensate16 (dgc_compensate16_clip) and of its multi-tensor
+// form k_compensate16_mt (dgc_compensate16_multi_clip: the batch's flat buffers with one
+// coefficient per tensor); DGC_CLIP_NONE is the unclipped kernel.
 #include "dgc_common.hpp"
 
 namespace dgc {
 
+// (The fused clip of a 16-bit gradient element: clip16 / clip_bound16, dgc_common.hpp.)
+// DGCSGDMemory.compensate of element i from its (clipped) gradient value gv
 template <int DT, bool NEST, bool ACC>
+__device__ __forceinline__ void comp16_at(float gv, uint16_t* __restrict__ mmt, uint16_t* __restrict__ vec,
+                                          uint16_t* __restrict__ out, float* __restrict__ vec32, int64_t i, float mom) {
+    float mv = h16_to_f32<DT>(mmt[i]);
+    float vv = ACC ? h16_to_f32<DT>(vec[i]) : 0.f, ov = 0.f;
+    if (NEST) {   // mmt.add_(grad).mul_(m); vec.add_(mmt).add_(grad) | out = mmt.add(grad)
+        mv = round16<DT>(__fadd_rn(mv, gv));
+        mv = round16<DT>(__fmul_rn(mv, mom));
+        if (ACC) {
+            vv = round16<DT>(__fadd_rn(vv, mv));
+            vv = round16<DT>(__fadd_rn(vv, gv));
+        } else {
+            ov = round16<DT>(__fadd_rn(mv, gv));
+        }
+    } else {      // mmt.mul_(m).add_(grad); vec.add_(mmt) | out = mmt.clone()
+        mv = round16<DT>(__fmul_rn(mv, mom));
+        mv = round16<DT>(__fadd_rn(mv, gv));
+        if (ACC)
+            vv = round16<DT>(__fadd_rn(vv, mv));
+        else
+            ov = mv;
+    }
+    mmt[i] = f32_to_h16<DT>(mv);
+    if (ACC) {
+        vec[i] = f32_to_h16<DT>(vv);
+        if (vec32) vec32[i] = vv;
+    } else {
+        out[i] = f32_to_h16<DT>(ov);
+    }
+}
+
+template <int DT, bool NEST, bool ACC, int CLIP>
 __global__ void __launch_bounds__(kBlock)
 k_compensate16(const uint16_t* __restrict__ g, uint16_t* __restrict__ mmt, uint16_t* __restrict__ vec,
-               uint16_t* __restrict__ out, float* __restrict__ vec32, int64_t n, float mom) {
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const float gv = h16_to_f32<DT>(g[i]);
-        float mv = h16_to_f32<DT>(mmt[i]);
-        float vv = ACC ? h16_to_f32<DT>(vec[i]) : 0.f, ov = 0.f;
-        if (NEST) {   // mmt.add_(grad).mul_(m); vec.add_(mmt).add_(grad) | out = mmt.add(grad)
-            mv = round16<DT>(__fadd_rn(mv, gv));
-            mv = round16<DT>(__fmul_rn(mv, mom));
-            if (ACC) {
-                vv = round16<DT>(__fadd_rn(vv, mv));
-                vv = round16<DT>(__fadd_rn(vv, gv));
-            } else {
-                ov = round16<DT>(__fadd_rn(mv, gv));
-            }
-        } else {      // mmt.mul_(m).add_(grad); vec.add_(mmt) | out = mmt.clone()
-            mv = round16<DT>(__fmul_rn(mv, mom));
-            mv = round16<DT>(__fadd_rn(mv, gv));
-            if (ACC)
-                vv = round16<DT>(__fadd_rn(vv, mv));
-            else
-                ov = mv;
-        }
-        mmt[i] = f32_to_h16<DT>(mv);
-        if (ACC) {
-            vec[i] = f32_to_h16<DT>(vv);
-            if (vec32) vec32[i] = vv;
-        } else {
-            out[i] = f32_to_h16<DT>(ov);
-        }
+               uint16_t* __restrict__ out, float* __restrict__ vec32, int64_t n, float mom, ClipArg ca) {
+    const float cf = clip_bound16<DT, CLIP>(ca, ca.tab ? ca.tab[0] : 0.f);
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+        comp16_at<DT, NEST, ACC>(clip16<DT, CLIP>(h16_to_f32<DT>(g[i]), cf), mmt, vec, out, vec32, i, mom);
+}
+
+// The batch's K1-16 with a clip: the tensors of the flat 16-bit buffers (tensor t's n[t]
+// elements at off[t], a multiple of 1024), one coefficient per tensor. A workgroup takes
+// 1024 elements of one tensor; the table rides in the arguments (<= 64 tensors per launch).
+// Only a tensor's own elements are touched: the padding between tensors stays +0, whatever
+// the clamp bound is.
+constexpr int kC16Max = 64;
+constexpr int kC16PerBlock = 1024;
+struct C16Chunk {
+    int32_t count, first;
+    int32_t bstart[kC16Max + 1];
+    int64_t n[kC16Max];
+    int64_t off[kC16Max];
+};
+
+template <int DT, bool NEST, int CLIP>
+__global__ void __launch_bounds__(kBlock)
+k_compensate16_mt(C16Chunk c, const uint16_t* __restrict__ g, uint16_t* __restrict__ mmt, uint16_t* __restrict__ vec,
+                  float* __restrict__ vec32, float mom, ClipArg ca) {
+    int lo = 0, hi = c.count - 1;
+    const int b = (int)blockIdx.x;
+    while (lo < hi) {   // bstart[lo] <= b < bstart[lo + 1]
+        const int mid = (lo + hi + 1) >> 1;
+        if (c.bstart[mid] <= b) lo = mid; else hi = mid - 1;
+    }
+    const int64_t n = c.n[lo], off = c.off[lo];
+    const float cf = clip_bound16<DT, CLIP>(ca, ca.tab ? ca.tab[c.first + lo] : 0.f);
+    const int64_t e0 = (int64_t)(b - c.bstart[lo]) * kC16PerBlock + threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < kC16PerBlock / kBlock; ++j) {
+        const int64_t e = e0 + (int64_t)j * kBlock;
+        if (e < n)
+            comp16_at<DT, NEST, true>(clip16<DT, CLIP>(h16_to_f32<DT>(g[off + e]), cf), mmt, vec, nullptr, vec32,
+                                      off + e, mom);
     }
 }
 
@@ -244,19 +291,70 @@ static int segsum16_t(const void* values, int32_t vd, const I* idx, int64_t tota
     return DGC_OK;
 }
 
+template <int DT, bool NEST, bool ACC>
+static void compensate16_clip_t(int32_t kind, int grid, hipStream_t s, const uint16_t* g, uint16_t* m, uint16_t* v,
+                                uint16_t* o, float* v32, int64_t n, float mom, ClipArg ca) {
+    if (kind == DGC_CLIP_SCALE)
+        hipLaunchKernelGGL((k_compensate16<DT, NEST, ACC, DGC_CLIP_SCALE>), dim3(grid), dim3(kBlock), 0, s, g, m, v, o, v32, n, mom, ca);
+    else if (kind == DGC_CLIP_CLAMP)
+        hipLaunchKernelGGL((k_compensate16<DT, NEST, ACC, DGC_CLIP_CLAMP>), dim3(grid), dim3(kBlock), 0, s, g, m, v, o, v32, n, mom, ca);
+    else
+        hipLaunchKernelGGL((k_compensate16<DT, NEST, ACC, DGC_CLIP_NONE>), dim3(grid), dim3(kBlock), 0, s, g, m, v, o, v32, n, mom, ca);
+}
+
 template <int DT>
 static int compensate16_t(const uint16_t* g, uint16_t* m, uint16_t* v, uint16_t* o, float* v32, int64_t n,
-                          float mom, bool nest, bool acc, hipStream_t s) {
+                          float mom, bool nest, bool acc, int32_t kind, ClipArg ca, hipStream_t s) {
     const int grid = grid_for(n);
     if (nest && acc)
-        hipLaunchKernelGGL((k_compensate16<DT, true, true>), dim3(grid), dim3(kBlock), 0, s, g, m, v, o, v32, n, mom);
+        compensate16_clip_t<DT, true, true>(kind, grid, s, g, m, v, o, v32, n, mom, ca);
     else if (nest)
-        hipLaunchKernelGGL((k_compensate16<DT, true, false>), dim3(grid), dim3(kBlock), 0, s, g, m, v, o, v32, n, mom);
+        compensate16_clip_t<DT, true, false>(kind, grid, s, g, m, v, o, v32, n, mom, ca);
     else if (acc)
-        hipLaunchKernelGGL((k_compensate16<DT, false, true>), dim3(grid), dim3(kBlock), 0, s, g, m, v, o, v32, n, mom);
+        compensate16_clip_t<DT, false, true>(kind, grid, s, g, m, v, o, v32, n, mom, ca);
     else
-        hipLaunchKernelGGL((k_compensate16<DT, false, false>), dim3(grid), dim3(kBlock), 0, s, g, m, v, o, v32, n, mom);
+        compensate16_clip_t<DT, false, false>(kind, grid, s, g, m, v, o, v32, n, mom, ca);
     DGC_LAUNCHED();
+    return DGC_OK;
+}
+
+template <int DT, bool NEST>
+static void compensate16_mt_t(int32_t kind, dim3 gd, hipStream_t s, const C16Chunk& c, const uint16_t* g, uint16_t* m,
+                              uint16_t* v, float* v32, float mom, ClipArg ca) {
+    if (kind == DGC_CLIP_SCALE)
+        hipLaunchKernelGGL((k_compensate16_mt<DT, NEST, DGC_CLIP_SCALE>), gd, dim3(kBlock), 0, s, c, g, m, v, v32, mom, ca);
+    else if (kind == DGC_CLIP_CLAMP)
+        hipLaunchKernelGGL((k_compensate16_mt<DT, NEST, DGC_CLIP_CLAMP>), gd, dim3(kBlock), 0, s, c, g, m, v, v32, mom, ca);
+    else
+        hipLaunchKernelGGL((k_compensate16_mt<DT, NEST, DGC_CLIP_NONE>), gd, dim3(kBlock), 0, s, c, g, m, v, v32, mom, ca);
+}
+
+// one chunk (<= kC16Max tensors from t0) of the table, checked
+static int compensate16_mt_chunk(const int64_t* numels, const int64_t* offsets, int32_t t0, int32_t count,
+                                 int64_t flat_numel, C16Chunk& c, int64_t& blocks) {
+    c = C16Chunk{};
+    c.first = t0;
+    c.count = count - t0 < kC16Max ? count - t0 : kC16Max;
+    blocks = 0;
+    for (int i = 0; i < c.count; ++i) {
+        const int64_t n = numels[t0 + i], off = offsets[t0 + i];
+        if (n < 0 || off < 0 || (off % kC16PerBlock) != 0 || off + n > flat_numel)
+            DGC_FAIL(DGC_ERR_INVALID, "dgc_compensate16_multi_clip: tensor %d: numel %lld at offset %lld (offsets are "
+                                      "multiples of 1024, tensors lie inside flat_numel)",
+                     t0 + i, (long long)n, (long long)off);
+        c.bstart[i] = (int32_t)blocks;
+        c.n[i] = n;
+        c.off[i] = off;
+        blocks += ceil_div(n, (int64_t)kC16PerBlock);
+        if (blocks > 0x7FFFFFFFLL) DGC_FAIL(DGC_ERR_INVALID, "dgc_compensate16_multi_clip: too many elements");
+    }
+    c.bstart[c.count] = (int32_t)blocks;
+    return DGC_OK;
+}
+
+static int clip16_check(int32_t kind, const float* clip, const char* who) {
+    if (!clip_kind_ok(kind)) DGC_FAIL(DGC_ERR_INVALID, "%s: clip kind %d", who, (int)kind);
+    if (kind == DGC_CLIP_SCALE && !clip) DGC_FAIL(DGC_ERR_INVALID, "%s: DGC_CLIP_SCALE needs the coefficient table", who);
     return DGC_OK;
 }
 
@@ -278,24 +376,75 @@ static int scatter16_t(const void* values, int32_t vd, const I* idx, const int64
     return DGC_OK;
 }
 
-}  // namespace dgc
-
-extern "C" int dgc_compensate16(const void* grad, void* mmt, void* vec, void* out, float* vec32, int64_t n,
-                                float momentum, int32_t nesterov, int32_t accumulate, int32_t dtype, void* stream) {
-    using namespace dgc;
-    if (!is16(dtype)) DGC_FAIL(DGC_ERR_DTYPE, "dgc_compensate16: dtype must be DGC_BF16 or DGC_F16");
-    if (n < 0) DGC_FAIL(DGC_ERR_INVALID, "dgc_compensate16: n < 0");
+static int compensate16(const char* who, const void* grad, void* mmt, void* vec, void* out, float* vec32, int64_t n,
+                        float momentum, int32_t nesterov, int32_t accumulate, int32_t dtype, int32_t kind,
+                        const float* clip, float clip_value, void* stream) {
+    if (!is16(dtype)) DGC_FAIL(DGC_ERR_DTYPE, "%s: dtype must be DGC_BF16 or DGC_F16", who);
+    DGC_TRY(clip16_check(kind, clip, who));
+    if (n < 0) DGC_FAIL(DGC_ERR_INVALID, "%s: n < 0", who);
     if (n == 0) return DGC_OK;
-    if (!grad || !mmt) DGC_FAIL(DGC_ERR_INVALID, "dgc_compensate16: null grad/mmt");
-    if (accumulate && !vec) DGC_FAIL(DGC_ERR_INVALID, "dgc_compensate16: accumulate needs vec");
-    if (!accumulate && !out) DGC_FAIL(DGC_ERR_INVALID, "dgc_compensate16: dense branch needs out");
+    if (!grad || !mmt) DGC_FAIL(DGC_ERR_INVALID, "%s: null grad/mmt", who);
+    if (accumulate && !vec) DGC_FAIL(DGC_ERR_INVALID, "%s: accumulate needs vec", who);
+    if (!accumulate && !out) DGC_FAIL(DGC_ERR_INVALID, "%s: dense branch needs out", who);
     auto g = static_cast<const uint16_t*>(grad);
     auto m = static_cast<uint16_t*>(mmt);
     auto v = static_cast<uint16_t*>(vec);
     auto o = static_cast<uint16_t*>(out);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == DGC_BF16 ? compensate16_t<DGC_BF16>(g, m, v, o, vec32, n, momentum, nesterov != 0, accumulate != 0, s)
-                             : compensate16_t<DGC_F16>(g, m, v, o, vec32, n, momentum, nesterov != 0, accumulate != 0, s);
+    const ClipArg ca{clip, clip_value};
+    return dtype == DGC_BF16
+               ? compensate16_t<DGC_BF16>(g, m, v, o, vec32, n, momentum, nesterov != 0, accumulate != 0, kind, ca, s)
+               : compensate16_t<DGC_F16>(g, m, v, o, vec32, n, momentum, nesterov != 0, accumulate != 0, kind, ca, s);
+}
+}  // namespace dgc
+
+extern "C" int dgc_compensate16(const void* grad, void* mmt, void* vec, void* out, float* vec32, int64_t n,
+                                float momentum, int32_t nesterov, int32_t accumulate, int32_t dtype, void* stream) {
+    return dgc::compensate16("dgc_compensate16", grad, mmt, vec, out, vec32, n, momentum, nesterov, accumulate, dtype,
+                             DGC_CLIP_NONE, nullptr, 0.f, stream);
+}
+
+extern "C" int dgc_compensate16_clip(const void* grad, void* mmt, void* vec, void* out, float* vec32, int64_t n,
+                                     float momentum, int32_t nesterov, int32_t accumulate, int32_t dtype,
+                                     int32_t clip_kind, const float* clip, float clip_value, void* stream) {
+    return dgc::compensate16("dgc_compensate16_clip", grad, mmt, vec, out, vec32, n, momentum, nesterov, accumulate,
+                             dtype, clip_kind, clip, clip_value, stream);
+}
+
+extern "C" int dgc_compensate16_multi_clip(const void* grad, void* mmt, void* vec, float* vec32,
+                                           const int64_t* numels, const int64_t* offsets, int32_t count,
+                                           int64_t flat_numel, float momentum, int32_t nesterov, int32_t dtype,
+                                           int32_t clip_kind, const float* clip, float clip_value, void* stream) {
+    using namespace dgc;
+    const char* who = "dgc_compensate16_multi_clip";
+    if (!is16(dtype)) DGC_FAIL(DGC_ERR_DTYPE, "%s: dtype must be DGC_BF16 or DGC_F16", who);
+    DGC_TRY(clip16_check(clip_kind, clip, who));
+    if (count < 0 || flat_numel < 0) DGC_FAIL(DGC_ERR_INVALID, "%s: count or flat_numel < 0", who);
+    if (count == 0) return DGC_OK;
+    if (!grad || !mmt || !vec || !numels || !offsets) DGC_FAIL(DGC_ERR_INVALID, "%s: null argument", who);
+    C16Chunk c;
+    int64_t blocks;
+    for (int32_t t0 = 0; t0 < count; t0 += kC16Max)   // the whole table is checked before the first launch
+        DGC_TRY(compensate16_mt_chunk(numels, offsets, t0, count, flat_numel, c, blocks));
+    auto g = static_cast<const uint16_t*>(grad);
+    auto m = static_cast<uint16_t*>(mmt);
+    auto v = static_cast<uint16_t*>(vec);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const ClipArg ca{clip, clip_value};
+    for (int32_t t0 = 0; t0 < count; t0 += kC16Max) {
+        DGC_TRY(compensate16_mt_chunk(numels, offsets, t0, count, flat_numel, c, blocks));
+        if (blocks == 0) continue;
+        const dim3 gd((unsigned)blocks);
+        if (dtype == DGC_BF16) {
+            if (nesterov) compensate16_mt_t<DGC_BF16, true>(clip_kind, gd, s, c, g, m, v, vec32, momentum, ca);
+            else compensate16_mt_t<DGC_BF16, false>(clip_kind, gd, s, c, g, m, v, vec32, momentum, ca);
+        } else {
+            if (nesterov) compensate16_mt_t<DGC_F16, true>(clip_kind, gd, s, c, g, m, v, vec32, momentum, ca);
+            else compensate16_mt_t<DGC_F16, false>(clip_kind, gd, s, c, g, m, v, vec32, momentum, ca);
+        }
+        DGC_LAUNCHED();
+    }
+    return DGC_OK;
 }
 
 extern "C" int dgc_widen16(const void* x, float* y, int64_t n, int32_t dtype, void* stream) {

@@ -653,44 +653,52 @@ int compress_begin(const float* grad, float* mmt, float* vec, float momentum, bo
 // dgc_compress_finish(vec32, null, ...) then serves the image. mmt, vec and vec32 hold
 // ceil(numel / 1024) * 1024 elements. There is no unfused fallback: what the listing
 // kernel cannot take is refused.
-template <int DT>
-static void launch_k1_16(bool nesterov, dim3 gd, hipStream_t s, const uint16_t* grad, uint16_t* mmt,
-                         uint16_t* vec, float* vec32, float momentum, const SelWS& w, int64_t start, int wt,
-                         const OneTable& ot) {
-    if (nesterov)
-        hipLaunchKernelGGL((k_compensate_list16<DT, true>), gd, dim3(kBlock), 0, s, grad, mmt, vec, vec32, momentum,
-                           w, start, wt, ot);
+template <int DT, bool NEST, typename... Args>
+static void launch_k1_16_clip(int32_t clip_kind, dim3 gd, hipStream_t s, Args... args) {
+    if (clip_kind == DGC_CLIP_SCALE)
+        hipLaunchKernelGGL((k_compensate_list16<DT, NEST, DGC_CLIP_SCALE>), gd, dim3(kBlock), 0, s, args...);
+    else if (clip_kind == DGC_CLIP_CLAMP)
+        hipLaunchKernelGGL((k_compensate_list16<DT, NEST, DGC_CLIP_CLAMP>), gd, dim3(kBlock), 0, s, args...);
     else
-        hipLaunchKernelGGL((k_compensate_list16<DT, false>), gd, dim3(kBlock), 0, s, grad, mmt, vec, vec32, momentum,
-                           w, start, wt, ot);
+        hipLaunchKernelGGL((k_compensate_list16<DT, NEST, DGC_CLIP_NONE>), gd, dim3(kBlock), 0, s, args...);
+}
+
+template <int DT>
+static void launch_k1_16(bool nesterov, int32_t clip_kind, dim3 gd, hipStream_t s, const uint16_t* grad,
+                         uint16_t* mmt, uint16_t* vec, float* vec32, float momentum, const SelWS& w, int64_t start,
+                         int wt, const OneTable& ot, ClipArg ca) {
+    if (nesterov) launch_k1_16_clip<DT, true>(clip_kind, gd, s, grad, mmt, vec, vec32, momentum, w, start, wt, ot, ca);
+    else launch_k1_16_clip<DT, false>(clip_kind, gd, s, grad, mmt, vec, vec32, momentum, w, start, wt, ot, ca);
 }
 
 int compress_begin16(const void* grad, void* mmt, void* vec, float* vec32, float momentum, bool nesterov,
                      int64_t s_start, int64_t s_stride, const dgc_select_params* p, float* spec, void* ws,
-                     size_t ws_bytes, int32_t dtype, hipStream_t s) {
+                     size_t ws_bytes, int32_t dtype, hipStream_t s, int32_t clip_kind = DGC_CLIP_NONE,
+                     ClipArg ca = ClipArg{nullptr, 0.f}, const char* who = "dgc_compress_begin16") {
     if (dtype != DGC_BF16 && dtype != DGC_F16)
-        DGC_FAIL(DGC_ERR_INVALID, "dgc_compress_begin16: dtype must be DGC_BF16 or DGC_F16 (got %d)", (int)dtype);
+        DGC_FAIL(DGC_ERR_INVALID, "%s: dtype must be DGC_BF16 or DGC_F16 (got %d)", who, (int)dtype);
     if (!grad || !mmt || !vec || !vec32 || !p)
-        DGC_FAIL(DGC_ERR_INVALID, "dgc_compress_begin16: null grad/mmt/vec/vec32/params");
+        DGC_FAIL(DGC_ERR_INVALID, "%s: null grad/mmt/vec/vec32/params", who);
+    DGC_TRY(k1_clip_check(clip_kind, ca.tab, who));
     if (p->update_memory != 0)
-        DGC_FAIL(DGC_ERR_INVALID, "dgc_compress_begin16: update_memory must be 0 (the 16-bit state is masked from "
-                                  "the payload, dgc_mask_packed16)");
+        DGC_FAIL(DGC_ERR_INVALID, "%s: update_memory must be 0 (the 16-bit state is masked from "
+                                  "the payload, dgc_mask_packed16)", who);
     if (p->thr_dtype != dtype)
-        DGC_FAIL(DGC_ERR_INVALID, "dgc_compress_begin16: params.thr_dtype %d must be the dtype %d", (int)p->thr_dtype,
+        DGC_FAIL(DGC_ERR_INVALID, "%s: params.thr_dtype %d must be the dtype %d", who, (int)p->thr_dtype,
                  (int)dtype);
     DGC_TRY(compress_check(p, nullptr, nullptr, s_start, s_stride, 1, false));
     const int64_t n = p->numel;
     const bool sampled = n != p->num_samples;
     if (!aligned16(grad) || !aligned16(mmt) || !aligned16(vec) || !aligned16(vec32))
-        DGC_FAIL(DGC_ERR_INVALID, "dgc_compress_begin16: grad, mmt, vec and vec32 must be 16-B aligned");
+        DGC_FAIL(DGC_ERR_INVALID, "%s: grad, mmt, vec and vec32 must be 16-B aligned", who);
     if (!k1_stride_ok(sampled, s_stride))
-        DGC_FAIL(DGC_ERR_INVALID, "dgc_compress_begin16: sample stride %lld outside [4, 2^30)", (long long)s_stride);
+        DGC_FAIL(DGC_ERR_INVALID, "%s: sample stride %lld outside [4, 2^30)", who, (long long)s_stride);
     Layout L;
     SelWS w;
     OneTable ot{};
     DGC_TRY(one_ws(p, s_start, s_stride, 1, spec, ws, ws_bytes, L, w, ot));
     if (L.grid[BT_K1] < 1 || L.grid[BT_K1] > 0x7FFFFFFFLL)
-        DGC_FAIL(DGC_ERR_INVALID, "dgc_compress_begin16: n too large");
+        DGC_FAIL(DGC_ERR_INVALID, "%s: n too large", who);
     // No kK1FlatLds here: a wave of this kernel has 6 KB of loads in flight where the fp32
     // one has 12, and held to 3 waves per SIMD it ran slower. Same box, 1e9 elements, K1-16
     // ms: 3 waves (48 KB of LDS asked for) 2.47-2.49, 6 waves (24 KB) 2.28, the registers'
@@ -701,9 +709,9 @@ int compress_begin16(const void* grad, void* mmt, void* vec, float* vec32, float
     const uint16_t* g16 = static_cast<const uint16_t*>(grad);
     uint16_t *m16 = static_cast<uint16_t*>(mmt), *v16 = static_cast<uint16_t*>(vec);
     if (dtype == DGC_BF16)
-        launch_k1_16<DGC_BF16>(nesterov, gd, s, g16, m16, v16, vec32, momentum, w, ot.start, (int)wt, ot);
+        launch_k1_16<DGC_BF16>(nesterov, clip_kind, gd, s, g16, m16, v16, vec32, momentum, w, ot.start, (int)wt, ot, ca);
     else
-        launch_k1_16<DGC_F16>(nesterov, gd, s, g16, m16, v16, vec32, momentum, w, ot.start, (int)wt, ot);
+        launch_k1_16<DGC_F16>(nesterov, clip_kind, gd, s, g16, m16, v16, vec32, momentum, w, ot.start, (int)wt, ot, ca);
     DGC_LAUNCHED();
     return DGC_OK;
 }
@@ -1016,6 +1024,17 @@ extern "C" int dgc_compress_begin16(const void* grad, void* mmt, void* vec, floa
     return dgc::compress_begin16(grad, mmt, vec, vec32, momentum, nesterov != 0, sample_start, sample_stride, params,
                                  const_cast<float*>(spec_threshold), ws, ws_bytes, dtype,
                                  static_cast<hipStream_t>(stream));
+}
+
+extern "C" int dgc_compress_begin16_clip(const void* grad, void* mmt, void* vec, float* vec32, float momentum,
+                                         int32_t nesterov, int64_t sample_start, int64_t sample_stride,
+                                         const dgc_select_params* params, const float* spec_threshold,
+                                         int32_t clip_kind, const float* clip, float clip_value, void* ws,
+                                         size_t ws_bytes, int32_t dtype, void* stream) {
+    return dgc::compress_begin16(grad, mmt, vec, vec32, momentum, nesterov != 0, sample_start, sample_stride, params,
+                                 const_cast<float*>(spec_threshold), ws, ws_bytes, dtype,
+                                 static_cast<hipStream_t>(stream), clip_kind, dgc::ClipArg{clip, clip_value},
+                                 "dgc_compress_begin16_clip");
 }
 
 extern "C" int dgc_compress_finish(float* vec, float* mmt, int64_t sample_start, int64_t sample_stride,

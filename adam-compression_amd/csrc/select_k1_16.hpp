@@ -33,6 +33,13 @@
 //
 // No deferred masking: the 16-bit state is masked from the payload right after the
 // selection (dgc_mask_packed16), which runs pure on the image.
+//
+// CLIP: the gradient clipped once it is unpacked, as the reference's clip leaves a 16-bit
+// tensor (clip16, dgc_common.hpp: the product rounded to the dtype; the clamp against the bound rounded to
+// the dtype). The tensor's coefficient is one more state word: a wave-uniform load issued
+// with the others, ahead of the streaming loads and of every store (a null table is
+// replaced by the tensor's own state, as K1 does). DGC_CLIP_NONE compiles to the unclipped
+// kernel.
 #pragma once
 #include "select_k1.hpp"
 
@@ -90,10 +97,10 @@ __device__ __forceinline__ float comp16(float g, float& m, float& v, float mom) 
     return v;
 }
 
-template <int DT, bool NEST>
+template <int DT, bool NEST, int CLIP>
 __global__ void __launch_bounds__(kBlock)
 k_compensate_list16(const uint16_t* __restrict__ g16, uint16_t* __restrict__ mmt16, uint16_t* __restrict__ vec16,
-                    float* __restrict__ img, float mom, SelWS w, int64_t start, int wt, OneTable ot) {
+                    float* __restrict__ img, float mom, SelWS w, int64_t start, int wt, OneTable ot, ClipArg ca) {
     const TDesc d = ot.d;   // by value: stores below cannot alias it
     const int lane = threadIdx.x & 63, wave = wave_id();
     const int64_t ls = (int64_t)blockIdx.x * kSegPerBlock4 + wave;   // local segment
@@ -108,6 +115,8 @@ k_compensate_list16(const uint16_t* __restrict__ g16, uint16_t* __restrict__ mmt
     DGC_GLB const float* spec = w.spec ? glb(w.spec) : &st->t0;   // (null: any readable words)
     const float spec0 = spec[0], spec2 = spec[2];
     const int32_t epoch = st->epoch;
+    float cf_tab = 0.f;
+    if (CLIP != DGC_CLIP_NONE) cf_tab = *(ca.tab ? glb(ca.tab) : (DGC_GLB const float*)&st->t0);
 
     // ---- the streaming loads: momentum and velocity (padded: whole groups), then the
     // gradient's full groups
@@ -151,6 +160,7 @@ k_compensate_list16(const uint16_t* __restrict__ g16, uint16_t* __restrict__ mmt
     const K1Seg k = k1_segment_begin(w, d, 0, st, first, true, spec0, spec2, epoch, ls, start, scount);
     uint32_t c = 0, mk = 0;
     const int64_t seg = d.seg0 + ls;
+    const float cf = clip_bound16<DT, CLIP>(ca, cf_tab);
 #pragma unroll
     for (int u = 0; u < kSegTiles; ++u) {
         const int64_t e = 4 * (seg4 + u * 64 + lane);
@@ -171,7 +181,7 @@ k_compensate_list16(const uint16_t* __restrict__ g16, uint16_t* __restrict__ mmt
             unpack4<DT>(vv[u], x);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                comp16<DT, NEST>(gx[j], mx[j], x[j], mom);
+                comp16<DT, NEST>(clip16<DT, CLIP>(gx[j], cf), mx[j], x[j], mom);
                 if (!((valid >> j) & 1u)) mx[j] = x[j] = 0.f;   // padding stays +0
             }
             st_nt(mmt + u * 64 + lane, pack4<DT>(mx));

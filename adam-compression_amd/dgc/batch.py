@@ -53,11 +53,13 @@ class DGCBatch(ReceiveSide):
         self.dtype = dtype
         self.half = dtype in _lib.HALF
         # local gradient clipping fused into K1: a dgc.clip_grad.ClipSpec (norm-2, norm-inf
-        # or value; fp32) — one statistic per tensor over K1's own pointer table, the
-        # coefficients, then the clipped K1: three more launches per step up to 64 tensors
-        if clip is not None and (self.half or not getattr(clip, "batchable", False)):
-            raise NotImplementedError(f"DGCBatch: clip takes a local dgc.clip_grad spec (norm-2, norm-inf or value) "
-                                      f"on fp32 parameters (got {clip!r} on {dtype})")
+        # or value) — one statistic per tensor over K1's own pointer table, the
+        # coefficients, then the clipped K1: three more launches per step up to 64 tensors.
+        # 16-bit: the statistics over the flat buffer's tensors (dgc_grad_stats16), the
+        # coefficients in the dtype, then the multi-tensor K1-16 (dgc_compensate16_multi_clip)
+        if clip is not None and not getattr(clip, "batchable", False):
+            raise NotImplementedError(f"DGCBatch: clip takes a local dgc.clip_grad spec (norm-2, norm-inf or value; "
+                                      f"got {clip!r})")
         self.clip = clip
         self.clip_coefs = None   # device float[T] of the last step (None: a fixed clamp)
         self._fill = fill
@@ -217,6 +219,19 @@ class DGCBatch(ReceiveSide):
                 numels, offs = self._arrays16()
                 _lib.check(L.dgc_gather16(grad_ptrs, numels, offs, len(self.names), self.grad_flat.data_ptr(), st),
                            "dgc_gather16")
+            if self.clip is not None:
+                T = len(self.names)
+                numels, offs = self._arrays16()
+                base = self.grad_flat.data_ptr()
+                flat_ptrs = (ctypes.c_void_p * T)(*[base + 2 * o for o in self.offsets])
+                self.clip_coefs = self.clip.table_coefs(flat_ptrs, numels, T, self.device, dtype=self.dtype)
+                _lib.check(L.dgc_compensate16_multi_clip(self.grad_flat.data_ptr(), self._mmt_flat.data_ptr(),
+                                                         self._vec_flat.data_ptr(), self._vec32.data_ptr(), numels,
+                                                         offs, T, self.flat_numel, self.momentum, int(self.nesterov),
+                                                         _lib.VD[self.dtype], self.clip.kind,
+                                                         _lib.ptr(self.clip_coefs), self.clip.param, st),
+                           "dgc_compensate16_multi_clip")
+                return
             _lib.check(L.dgc_compensate16(self.grad_flat.data_ptr(), self._mmt_flat.data_ptr(),
                                           self._vec_flat.data_ptr(), None, self._vec32.data_ptr(), self.flat_numel,
                                           self.momentum, int(self.nesterov), 1, _lib.VD[self.dtype], st),

@@ -33,6 +33,14 @@ pure on the image and the 16-bit state is masked from the payload
 (``dgc_mask_packed16``), so nothing is ever deferred. The receive side is the 16-bit
 packed decompress (``dgc_decompress_packed16``: dense fill, one exchange part).
 
+``clip=``: the reference's local gradient clipping (a ``dgc.clip_grad.ClipSpec``, or one of
+``clip_grad_norm_`` (norm 2 / inf) / ``clip_grad_value_``, bare or as a ``functools.partial``)
+fused into K1's load of the gradient: the bucket's statistic (``dgc_grad_stats`` /
+``dgc_grad_stats16``), the coefficient (``dgc_clip_coefs`` / ``dgc_clip_coefs16``), then
+``dgc_compress_begin_clip`` / ``dgc_compress_begin16_clip`` — stream-ordered, nothing read
+back; ``clip_coef`` holds the device coefficient of the last step. The gradient stays as
+it was.
+
 The numerics are those of the drop-in ``DGCCompressor`` + ``DGCSGDMemory`` (same
 kernels); the sample start is drawn from a ``random.Random`` seeded identically on
 every rank, one draw per step, like the reference's global ``random`` call.
@@ -45,6 +53,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
+from . import clip_grad
 from .compression import DGCCompressor
 from .exchange import ReceiveSide, Receiver
 
@@ -70,7 +79,7 @@ class DGCBucket(ReceiveSide):
                  sample_ratio=0.01, compress_upper_bound=1.3, compress_lower_bound=0.8,
                  max_adaptation_iters=10, resample=True, fp16_values=False, int32_indices=False,
                  device=None, world_size=None, seed=42, fill="auto", deferred_masking=True, exchange_parts="auto",
-                 resample_order="topk", dtype=torch.float32):
+                 resample_order="topk", dtype=torch.float32, clip=None):
         if fill not in ("auto", "inline", "allgather", "sparse"):
             raise ValueError(f"fill must be 'auto', 'inline', 'allgather' or 'sparse', not {fill!r}")
         if dtype not in (torch.float32,) + _lib.HALF:
@@ -80,6 +89,14 @@ class DGCBucket(ReceiveSide):
         if self.half and fill in ("allgather", "sparse"):
             raise NotImplementedError(f"DGCBucket: fill={fill!r} on {dtype} parameters (the 16-bit decompress is the "
                                       "dense fill with the scatter)")
+        if clip is not None:
+            spec = clip if isinstance(clip, clip_grad.ClipSpec) else clip_grad.spec_of(clip)
+            if spec is None or not spec.batchable:
+                raise NotImplementedError(f"DGCBucket: clip takes a local dgc.clip_grad function or spec (norm-2, "
+                                          f"norm-inf or value; got {clip!r})")
+            clip = spec
+        self.clip = clip
+        self.clip_coef = None   # device float[1] of the last step (None: no clip, or a fixed clamp)
         self.device = torch.device(device or "cuda")
         self.numel = N = int(numel)
         self.k, self.num_samples, self.top_k_samples, self.stride = DGCCompressor._attributes(
@@ -133,6 +150,8 @@ class DGCBucket(ReceiveSide):
         self.rx = Receiver(self.k, N, self.world, self.vdtype, self.idtype, dev, self.status, fill, exchange_parts,
                            dtype=dtype, unsent="DGCBucket: decompress of a split exchange before exchange()")
         self._L = L
+        if clip is not None:
+            self._clip_numel = (ctypes.c_int64 * 1)(N)
         if self.fill in ("allgather", "sparse"):
             self.side = torch.cuda.Stream(device=dev)
             self._ev_go = torch.cuda.Event()
@@ -175,16 +194,37 @@ class DGCBucket(ReceiveSide):
                     and grad.numel() == self.numel and grad.data_ptr() % 16 == 0):
                 raise ValueError(f"DGCBucket.compensate: grad must be a contiguous, 16-B aligned {self.dtype} CUDA "
                                  f"tensor of {self.numel} elements")
+            if self.clip is not None:
+                self.clip_coef = self.clip.table_coefs((ctypes.c_void_p * 1)(grad.data_ptr()), self._clip_numel, 1,
+                                                       self.device, dtype=self.dtype)
+                _lib.check(L.dgc_compress_begin16_clip(grad.data_ptr(), self._mmt.data_ptr(), self._vec.data_ptr(),
+                                                       self._vec32.data_ptr(), self.momentum, int(self.nesterov),
+                                                       self.start, self.stride, ctypes.byref(self.params),
+                                                       self.spec.data_ptr(), self.clip.kind, _lib.ptr(self.clip_coef),
+                                                       self.clip.param, self.ws.data_ptr(), self.ws.numel(),
+                                                       _lib.VD[self.dtype], _lib.stream_of(self.device)),
+                           "dgc_compress_begin16_clip")
+                return
             _lib.check(L.dgc_compress_begin16(grad.data_ptr(), self._mmt.data_ptr(), self._vec.data_ptr(),
                                               self._vec32.data_ptr(), self.momentum, int(self.nesterov), self.start,
                                               self.stride, ctypes.byref(self.params), self.spec.data_ptr(),
                                               self.ws.data_ptr(), self.ws.numel(), _lib.VD[self.dtype],
                                               _lib.stream_of(self.device)), "dgc_compress_begin16")
             return
-        _lib.check(L.dgc_compress_begin(grad.data_ptr(), self._mmt.data_ptr(), self._vec.data_ptr(), self.momentum,
-                                        int(self.nesterov), self.start, self.stride, ctypes.byref(self.params),
-                                        self.spec.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
-                                        _lib.stream_of(self.device)), "dgc_compress_begin")
+        if self.clip is not None:
+            self.clip_coef = self.clip.table_coefs((ctypes.c_void_p * 1)(grad.data_ptr()), self._clip_numel, 1,
+                                                   self.device)
+            _lib.check(L.dgc_compress_begin_clip(grad.data_ptr(), self._mmt.data_ptr(), self._vec.data_ptr(),
+                                                 self.momentum, int(self.nesterov), self.start, self.stride,
+                                                 ctypes.byref(self.params), self.spec.data_ptr(), self.clip.kind,
+                                                 _lib.ptr(self.clip_coef), self.clip.param, self.ws.data_ptr(),
+                                                 self.ws.numel(), _lib.stream_of(self.device)),
+                       "dgc_compress_begin_clip")
+        else:
+            _lib.check(L.dgc_compress_begin(grad.data_ptr(), self._mmt.data_ptr(), self._vec.data_ptr(),
+                                            self.momentum, int(self.nesterov), self.start, self.stride,
+                                            ctypes.byref(self.params), self.spec.data_ptr(), self.ws.data_ptr(),
+                                            self.ws.numel(), _lib.stream_of(self.device)), "dgc_compress_begin")
         self._pending = False   # K1 applied it
 
     def select(self):

@@ -25,8 +25,12 @@ One deviation: every function returns the tensor. The reference's ``clip_grad_va
 clip into K1's load of the gradient instead of calling them: the clipped value is then
 formed in registers and the input gradient stays as it was.
 
-bf16 / fp16 tensors take the reference's formula in ATen ops on the device (each op
-rounds to the dtype, as the reference's do), without a host synchronisation.
+Called directly on a bf16 / fp16 tensor, the module functions take the reference's formula
+in ATen ops on the device (each op rounds to the dtype, as the reference's do), without a
+host synchronisation. Fused (``ClipSpec.fusable``), a local clip of a 16-bit gradient is the
+same three steps in the dtype's arithmetic: ``dgc_grad_stats16`` -> ``dgc_clip_coefs16`` ->
+the clip in K1-16's load (``dgc_compensate16_clip``, ``dgc_compensate16_multi_clip``,
+``dgc_compress_begin16_clip``).
 """
 import ctypes
 import functools
@@ -88,16 +92,32 @@ class ClipSpec:
         what ``DGCBatch`` and the batched optimizer take."""
         return self.mode in ("norm2", "norminf", "value")
 
+    def fusable(self, dtype):
+        """Whether the engines fuse this clip into K1's load of a gradient of ``dtype``: the
+        local clips on fp32 / bf16 / fp16, the global variants (and a p-norm, whose norm
+        torch takes) on fp32 only."""
+        return dtype == torch.float32 or (self.batchable and dtype in _lib.HALF)
+
     # ------------------------------------------------------------------ device steps
-    def table_coefs(self, ptrs, numels, count, device, round_to=torch.float32):
+    def table_coefs(self, ptrs, numels, count, device, round_to=torch.float32, dtype=torch.float32):
         """stats -> coefs over a ctypes table of ``count`` device pointers / numels:
-        the device float[count] coefficient table (None for the fixed clamp)."""
+        the device float[count] coefficient table (None for the fixed clamp). ``dtype``:
+        the tensors' (bf16 / fp16: the statistic and the coefficient in that dtype's
+        arithmetic, stored as fp32 images; a local clip only)."""
         if self.mode == "value":
             return None
         L, st = _lib.lib(), _lib.stream_of(device)
         stats = torch.empty(max(count, 1), dtype=torch.float32, device=device)
         wsz = L.dgc_grad_stats_workspace(numels, count)
         ws = torch.empty(wsz, dtype=torch.uint8, device=device)
+        if dtype in _lib.HALF:
+            if not self.batchable:
+                raise NotImplementedError(f"dgc.clip_grad: {self!r} is not fused on {dtype} tensors")
+            _lib.check(L.dgc_grad_stats16(ptrs, numels, count, self.stat, _lib.VD[dtype], _lib.ptr(stats),
+                                          _lib.ptr(ws), wsz, st), "dgc_grad_stats16")
+            _lib.check(L.dgc_clip_coefs16(_lib.ptr(stats), count, self.param, _lib.VD[dtype], _lib.ptr(stats), st),
+                       "dgc_clip_coefs16")
+            return stats
         _lib.check(L.dgc_grad_stats(ptrs, numels, count, self.stat, _lib.VD[round_to], _lib.ptr(stats), _lib.ptr(ws),
                                     wsz, st), "dgc_grad_stats")
         return self.coefs_of(stats, count)
@@ -113,9 +133,13 @@ class ClipSpec:
 
     def coef(self, g):
         """The device float[1] coefficient of the contiguous fp32 tensor ``g`` (None for
-        the fixed clamp)."""
+        the fixed clamp); of a bf16 / fp16 tensor for a local clip."""
         if self.mode == "value":
             return None
+        if g.dtype in _lib.HALF:
+            ptrs = (ctypes.c_void_p * 1)(g.data_ptr())
+            numels = (ctypes.c_int64 * 1)(g.numel())
+            return self.table_coefs(ptrs, numels, 1, g.device, dtype=g.dtype)
         if self.mode == "normp":
             stats = g.norm(self.norm_type).reshape(1)
             return self.coefs_of(stats, 1)

@@ -307,11 +307,13 @@ class DGCCompressor:
             if isinstance(mem, DGCSGDMemory) and dt in _lib.HALF:
                 # 16-bit state: K1-16 writes the velocity's fp32 image, the selection runs
                 # on it (pure), then DGCSGDMemory.update masks the 16-bit state
-                grad = mem._clip(tensor).reshape(-1).contiguous()
+                # a local dgc.clip_grad function: stats -> coefs, then the clip in K1-16's load
+                fused_clip = mem.fused_clip(tensor.reshape(-1)) if tensor.is_contiguous() else None
+                grad = (tensor if fused_clip is not None else mem._clip(tensor)).reshape(-1).contiguous()
                 mem._sync()
                 mem.state_of(name, grad, True, "DGCCompressor.compress")
                 img = self._ws.get(dev, 4 * numel, "img16")[: 4 * numel].view(torch.float32)
-                mem._compensate16(grad, name, True, vec32=img)
+                mem._compensate16(grad, name, True, vec32=img, clip=fused_clip)
                 _, idx, _, _, _ = self._select_on(img, name, dt, payload, lay, False)
                 mem.update(name, (idx,))
                 values, indices = self._views(payload, lay, idx.numel())

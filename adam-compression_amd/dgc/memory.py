@@ -11,8 +11,10 @@ The arithmetic runs in ``libdgc_hip.so`` on the MI355X:
 * ``gradient_clipping`` -> when it is one of ``dgc.clip_grad``'s functions (or a
   ``functools.partial`` of one) and the gradient is fp32: ``dgc_grad_stats`` ->
   ``dgc_clip_coefs`` -> ``dgc_compensate_clip``, the clip applied in registers as K1
-  loads the gradient (the input gradient stays as it was). Any other callable is called
-  as the reference calls it, before K1.
+  loads the gradient (the input gradient stays as it was). A local clip (norm-2,
+  norm-inf, value) of a bf16 / fp16 gradient is fused the same way, in the dtype's
+  arithmetic: ``dgc_grad_stats16`` -> ``dgc_clip_coefs16`` -> ``dgc_compensate16_clip``.
+  Any other callable is called as the reference calls it, before K1.
 
 ``momentums`` / ``velocities`` stay plain param-shaped tensors of the parameter's dtype
 keyed by name, so ``state_dict`` / ``load_state_dict`` and checkpoints are unchanged.
@@ -109,14 +111,19 @@ class DGCSGDMemory(Memory):
 
     def fused_clip(self, grad):
         """(clip kind, device coefficient or None, clamp value) for K1 when the clip of
-        ``grad`` (contiguous) can be fused: a recognised spec on an fp32 device tensor. The
-        statistic and the coefficient are issued here, stream-ordered; None otherwise."""
-        spec = self.clip_spec()
-        if spec is None or not (torch.is_tensor(grad) and grad.is_cuda and grad.dtype == torch.float32):
+        ``grad`` (contiguous) can be fused: a recognised spec on an fp32 device tensor, or a
+        local one on a bf16 / fp16 device tensor (``ClipSpec.fusable``). The statistic and
+        the coefficient are issued here, stream-ordered; None otherwise."""
+        if not self._fusable(grad):
             return None
-        _lib.require_cuda_f32(grad, "DGCSGDMemory.gradient_clipping")
+        spec = self.clip_spec()
+        _lib.require_cuda_float(grad, "DGCSGDMemory.gradient_clipping")
         coef = self.last_clip_coef = spec.coef(grad)
         return spec.kind, coef, spec.param
+
+    def _fusable(self, grad):
+        spec = self.clip_spec()
+        return spec is not None and torch.is_tensor(grad) and grad.is_cuda and spec.fusable(grad.dtype)
 
     def state_of(self, name, like, accumulate=True, what="DGCSGDMemory.compensate"):
         """(momentum, velocity or None) of ``name``, checked before their pointers reach a
@@ -144,8 +151,7 @@ class DGCSGDMemory(Memory):
         accumulate=True returns ``velocities[name]`` itself (updated in place);
         accumulate=False (dense tensors) returns a new tensor."""
         self._sync()
-        fusable = (self.clip_spec() is not None and torch.is_tensor(grad) and grad.is_cuda
-                   and grad.dtype == torch.float32)
+        fusable = self._fusable(grad)
         if not fusable:
             grad = self._clip(grad)
         g = grad.contiguous()
@@ -154,7 +160,7 @@ class DGCSGDMemory(Memory):
         L = _lib.lib()
         stream = _lib.stream_of(g.device)
         if dt in _lib.HALF:
-            return self._compensate16(g, name, accumulate)
+            return self._compensate16(g, name, accumulate, clip=self.fused_clip(g) if fusable else None)
         vec = self.velocities[name] if accumulate else None
         out = None if accumulate else torch.empty_like(mmt)
         args = (_lib.ptr(g), _lib.ptr(mmt), _lib.ptr(vec), _lib.ptr(out), mmt.numel(), float(self.momentum),
@@ -166,24 +172,24 @@ class DGCSGDMemory(Memory):
             _lib.check(L.dgc_compensate(*args, stream), "dgc_compensate")
         return vec if accumulate else out
 
-    def _compensate16(self, g, name, accumulate, vec32=None):
+    def _compensate16(self, g, name, accumulate, vec32=None, clip=None):
         """compensate on a bf16 / fp16 state (K1-16); vec32: optional fp32 image of the
-        new velocity for the selection (the compressor's fused path)."""
+        new velocity for the selection (the compressor's fused path); clip: ``fused_clip``'s
+        result, applied as K1-16 loads the gradient."""
         mmt, _ = self.state_of(name, g, accumulate)
         L = _lib.lib()
         dt = _lib.VD[g.dtype]
         stream = _lib.stream_of(g.device)
-        if accumulate:
-            vec = self.velocities[name]
-            _lib.check(L.dgc_compensate16(_lib.ptr(g), _lib.ptr(mmt), _lib.ptr(vec), None, _lib.ptr(vec32),
-                                          mmt.numel(), float(self.momentum), int(bool(self.nesterov)), 1, dt,
-                                          stream), "dgc_compensate16")
-            return vec
-        out = torch.empty_like(mmt)
-        _lib.check(L.dgc_compensate16(_lib.ptr(g), _lib.ptr(mmt), None, _lib.ptr(out), None, mmt.numel(),
-                                      float(self.momentum), int(bool(self.nesterov)), 0, dt, stream),
-                   "dgc_compensate16")
-        return out
+        vec = self.velocities[name] if accumulate else None
+        out = None if accumulate else torch.empty_like(mmt)
+        args = (_lib.ptr(g), _lib.ptr(mmt), _lib.ptr(vec), _lib.ptr(out), _lib.ptr(vec32) if accumulate else None,
+                mmt.numel(), float(self.momentum), int(bool(self.nesterov)), int(accumulate), dt)
+        if clip is None:
+            _lib.check(L.dgc_compensate16(*args, stream), "dgc_compensate16")
+        else:
+            kind, coef, value = clip
+            _lib.check(L.dgc_compensate16_clip(*args, kind, _lib.ptr(coef), value, stream), "dgc_compensate16_clip")
+        return vec if accumulate else out
 
     def update(self, name, ctx):
         """Zero the transmitted slots (dgc/memory.py:72-77)."""

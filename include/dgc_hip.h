@@ -568,7 +568,8 @@ int dgc_decompress_packed16(const void* payload, int32_t world, int64_t rank_str
  *   All four 16-B aligned; a sampled tensor's stride in [4, 2^30).
  * DGC_ERR_INVALID, before anything is launched, for any other dtype, a null pointer,
  * update_memory != 0, thr_dtype != dtype, a misaligned pointer or such a stride: there is
- * no unfused fallback. No clipping, no batch form. */
+ * no unfused fallback. The clipped form is dgc_compress_begin16_clip (K0-16 below); the
+ * batch's flat 16-bit buffers take dgc_compensate16 / dgc_compensate16_multi_clip. */
 int dgc_compress_begin16(const void* grad, void* mmt, void* vec, float* vec32, float momentum, int32_t nesterov,
                          int64_t sample_start, int64_t sample_stride, const dgc_select_params* params,
                          const float* spec_threshold, void* ws, size_t ws_bytes, int32_t dtype, void* stream);
@@ -646,6 +647,43 @@ int dgc_batch_compress_begin_ptrs_clip(const dgc_batch_desc* batch, const float*
 int dgc_compensate_multi_clip(const float* const* srcs, const int64_t* numels, const int64_t* offsets, int32_t count,
                               int32_t round_to, float* mmt, float* out, float momentum, int32_t nesterov,
                               int32_t clip_kind, const float* clip, float clip_value, void* stream);
+
+/* ---- K0-16: local gradient clipping of bf16 / fp16 tensors ----
+ * The reference's clip on a 16-bit tensor, every ATen op computed in fp32 and rounded to
+ * the dtype (rDT):
+ * dgc_grad_stats16: stats[t] = x.norm(2) (DGC_STAT_NORM2) or x.abs().max() (DGC_STAT_ABSMAX)
+ *   of the 16-bit tensor srcs[t][0..numels[t]) as a 0-dim tensor of the dtype holds it:
+ *   rDT(fl32(sqrt(sum x^2))) with the fp64 sum of dgc_grad_stats' fixed order — the value
+ *   dgc_grad_stats gives on the widened tensor, rounded to the dtype — stored as its fp32
+ *   image. An fp16 norm above 65504 is inf, as in the reference. srcs[t] 2-B aligned (8-B
+ *   aligned tensors are read by 8-B loads, others by 2-B loads; nothing past numel is
+ *   read); DGC_STAT_SUMSQ is refused. The workspace is dgc_grad_stats_workspace's.
+ * dgc_clip_coefs16: clip[t] = rDT(rDT(1 / rDT(stats[t] + 1e-6f)) * max_norm), the 0-dim
+ *   `max_norm / (total_norm + 1e-6)` of the dtype. stats and clip may be the same array.
+ * dgc_compensate16_clip / dgc_compress_begin16_clip: the calls they are named after with
+ *   g = rDT(clip(g, c)) applied as the gradient is loaded (the input stays as it was):
+ *   DGC_CLIP_SCALE with c = clip[0] (a value of the dtype, as dgc_clip_coefs16 leaves it),
+ *   DGC_CLIP_CLAMP with clip[0] or, clip = NULL, rDT(clip_value). DGC_CLIP_NONE is the
+ *   unclipped call.
+ * dgc_compensate16_multi_clip: dgc_compensate16 (accumulate) over the `count` tensors of
+ *   a batch's flat 16-bit buffers — tensor t's numels[t] elements at offsets[t] (HOST
+ *   arrays; offsets multiples of 1024, every tensor inside flat_numel) — with clip[t] per
+ *   tensor. Elements between the tensors are not touched. vec32 may be NULL.
+ * All arguments are checked before anything is launched. */
+int dgc_grad_stats16(const void* const* srcs, const int64_t* numels, int32_t count, int32_t kind, int32_t dtype,
+                     float* stats, void* ws, size_t ws_bytes, void* stream);
+int dgc_clip_coefs16(const float* stats, int32_t count, float max_norm, int32_t dtype, float* clip, void* stream);
+int dgc_compensate16_clip(const void* grad, void* mmt, void* vec, void* out, float* vec32, int64_t n, float momentum,
+                          int32_t nesterov, int32_t accumulate, int32_t dtype, int32_t clip_kind, const float* clip,
+                          float clip_value, void* stream);
+int dgc_compensate16_multi_clip(const void* grad, void* mmt, void* vec, float* vec32, const int64_t* numels,
+                                const int64_t* offsets, int32_t count, int64_t flat_numel, float momentum,
+                                int32_t nesterov, int32_t dtype, int32_t clip_kind, const float* clip,
+                                float clip_value, void* stream);
+int dgc_compress_begin16_clip(const void* grad, void* mmt, void* vec, float* vec32, float momentum, int32_t nesterov,
+                              int64_t sample_start, int64_t sample_stride, const dgc_select_params* params,
+                              const float* spec_threshold, int32_t clip_kind, const float* clip, float clip_value,
+                              void* ws, size_t ws_bytes, int32_t dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -44,7 +44,7 @@ without a warning:
   - loads and stores retire in issue order on their counter (true of gfx9 vector memory;
     scalar loads are only ever waited for with lgkmcnt(0) here).
 
-  tools/k1_isa.py                      # K1's twelve instantiations and K1-16's four, as a markdown table
+  tools/k1_isa.py                      # K1's twelve instantiations and K1-16's twelve, as a markdown table
   tools/k1_isa.py --compensate         # k_compensate4 / k_compensate_mt (compensate.hip)
   tools/k1_isa.py --asm FILE.s         # read an assembly file instead of compiling
   tools/k1_isa.py --trace 'ILb1ELb1ELi0E'   # the memory operations and waits of one kernel
@@ -265,9 +265,9 @@ def pretty(name):
     m = re.search(r"k_compensate_listILb(\d)ELb(\d)ELi(\d)E", name)
     if m:
         return "K1 NEST=%s ONE=%s CLIP=%s" % m.groups()
-    m = re.search(r"k_compensate_list16ILi(\d)ELb(\d)E", name)
+    m = re.search(r"k_compensate_list16ILi(\d)ELb(\d)ELi(\d)E", name)
     if m:
-        return "K1-16 DT=%s NEST=%s" % m.groups()
+        return "K1-16 DT=%s NEST=%s CLIP=%s" % m.groups()
     m = re.search(r"\d+(k_compensate\w*?)I(\w+?)EEv", name)
     return "%s<%s>" % m.groups() if m else name
 
