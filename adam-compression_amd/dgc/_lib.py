@@ -3,14 +3,20 @@
 The product path has no CPU fallback: if the library cannot be loaded, or a tensor
 is not a float tensor on an MI355X (fp32; bf16 / fp16 on the per-tensor path), every
 entry point raises.
+
+Every K1 call of the engines goes through its ``*_clip`` entry point with ``clip_args``:
+clipping is an argument (``NO_CLIP``: the unclipped call, include/dgc_hip.h), not a second
+call site. The unclipped entry points stay bound for tests, tools and older callers.
 """
 import ctypes
+import functools
+import math
 import os
 
 import torch
 
 __all__ = ["lib", "check", "stream_of", "ptr", "SelectParams", "SelectInfo", "Workspace",
-           "VD", "ID", "BRANCHES", "LIB_PATH", "available", "BatchDesc"]
+           "VD", "ID", "BRANCHES", "LIB_PATH", "available", "BatchDesc", "NO_CLIP", "clip_args", "select_params"]
 
 LIB_PATH = os.environ.get(
     "DGC_HIP_LIB",
@@ -27,6 +33,7 @@ HALF = (torch.bfloat16, torch.float16)   # 16-bit parameters (dgc_*16 entry poin
 ID = {torch.int64: 0, torch.int32: 1}
 BRANCHES = {0: "direct", 1: "ok", 2: "trunc", 3: "resample", 4: "exhausted"}
 TIE_RULES = {0: "none", 1: "exact", 2: "set"}
+NO_CLIP = (0, None, 0.0)   # (DGC_CLIP_NONE, no coefficient, no clamp value): clip_args(None)
 
 
 class SelectParams(ctypes.Structure):
@@ -297,7 +304,10 @@ def _load():
     try:
         handle = ctypes.CDLL(LIB_PATH)
         # DGC_LIB_PARTIAL=1 (same-box A/B against an older build, tools/ab_bench.py):
-        # symbols the older library lacks stay unbound instead of failing the load
+        # symbols the older library lacks stay unbound instead of failing the load. The
+        # engines call the *_clip entry points for every K1 (clip_args), so an A/B through
+        # them only works against a library that exports all seven (the newest is
+        # dgc_compress_begin16_clip)
         partial = os.environ.get("DGC_LIB_PARTIAL") == "1"
         for name, (res, args) in _SIGNATURES.items():
             if partial and not hasattr(handle, name):
@@ -368,14 +378,60 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def require_cuda_float(t, what, contiguous=True):
-    """A contiguous fp32, bf16 or fp16 tensor on the MI355X (the per-tensor path takes all
-    three; the engines take fp32 only: require_cuda_f32). Returns its dtype."""
+def clip_args(clip):
+    """The (clip_kind, clip, clip_value) arguments of a ``*_clip`` entry point from
+    ``DGCSGDMemory.fused_clip``'s triple (kind, device coefficient tensor or None, clamp
+    value); None is the unclipped call."""
+    if clip is None:
+        return NO_CLIP
+    kind, coef, value = clip
+    return kind, ptr(coef), value
+
+
+@functools.lru_cache(maxsize=None)
+def itemsize(dtype):
+    return torch.empty(0, dtype=dtype).element_size()
+
+
+def payload_views(buf, voff, ioff, vdtype, idtype, n):
+    """(values, indices): the first ``n`` entries of one rank's packed payload ``buf``
+    (uint8, 1-D; the byte offsets are ``payload_layout``'s) as 1-D views."""
+    return (buf[voff: voff + n * itemsize(vdtype)].view(vdtype),
+            buf[ioff: ioff + n * itemsize(idtype)].view(idtype))
+
+
+def select_params(numel, num_selects, num_samples, upper, lower, max_iters, resample, masking, update_memory,
+                  vdtype, idtype, thr_dtype=torch.float32, resample_order="topk", status_sink=None):
+    """A filled dgc_select_params: ``vdtype`` / ``idtype`` are the payload's, ``thr_dtype``
+    the dtype the threshold *= bound products round to (the tensor's)."""
+    p = SelectParams()
+    p.numel, p.num_selects, p.num_samples = numel, num_selects, num_samples
+    # n > k * upper  and  n < lower * k compare an int with a Python double
+    p.upper_count = math.floor(num_selects * upper)
+    p.lower_count = math.ceil(lower * num_selects)
+    p.upper, p.lower = float(upper), float(lower)
+    p.max_iters, p.resample, p.masking = int(max_iters), int(bool(resample)), int(bool(masking))
+    p.vdtype, p.idtype, p.thr_dtype = VD[vdtype], ID[idtype], VD[thr_dtype]
+    p.update_memory = int(update_memory)
+    p.resample_order = resample_order_flag(resample_order)
+    p.status_sink = status_sink
+    return p
+
+
+_DTYPE_NAMES = {torch.float32: "fp32", torch.bfloat16: "bf16", torch.float16: "fp16"}
+
+
+def require_cuda_float(t, what, contiguous=True, dtypes=(torch.float32,) + HALF):
+    """A contiguous tensor on the MI355X of one of ``dtypes`` (the per-tensor path takes
+    fp32, bf16 and fp16; the engines pass fp32 alone). The device is checked before
+    anything else. Returns its dtype."""
     if not (torch.is_tensor(t) and t.is_cuda):
         raise RuntimeError(f"{what}: the DGC hot path runs on the MI355X only (got a "
                            f"{'CPU' if torch.is_tensor(t) else type(t).__name__} tensor)")
-    if t.dtype not in (torch.float32,) + HALF:
-        raise NotImplementedError(f"{what}: fp32, bf16 or fp16 tensors only (got {t.dtype})")
+    if t.dtype not in dtypes:
+        names = [_DTYPE_NAMES[d] for d in dtypes]
+        raise NotImplementedError(f"{what}: {' or '.join(filter(None, (', '.join(names[:-1]), names[-1])))} tensors "
+                                  f"only (got {t.dtype})")
     if contiguous and not t.is_contiguous():
         raise ValueError(f"{what}: tensor must be contiguous")
     return t.dtype
@@ -394,16 +450,6 @@ def mask_packed16(payload, capacity, vdtype, idtype, mmt, vec, numel, device):
     the payload's indices zeroed in ``vec`` and, unless None, in ``mmt``."""
     check(lib().dgc_mask_packed16(payload.data_ptr(), capacity, VD[vdtype], ID[idtype], ptr(mmt), vec.data_ptr(), numel,
                                   stream_of(device)), "dgc_mask_packed16")
-
-
-def require_cuda_f32(t, what):
-    if not (torch.is_tensor(t) and t.is_cuda):
-        raise RuntimeError(f"{what}: the DGC hot path runs on the MI355X only (got a "
-                           f"{'CPU' if torch.is_tensor(t) else type(t).__name__} tensor)")
-    if t.dtype != torch.float32:
-        raise NotImplementedError(f"{what}: fp32 tensors only (got {t.dtype})")
-    if not t.is_contiguous():
-        raise ValueError(f"{what}: tensor must be contiguous")
 
 
 class Workspace:

@@ -10,7 +10,9 @@ tensors side by side in three flat fp32 buffers (gradients, momentums, velocitie
 each tensor at a 1024-element-aligned offset) and runs
 
     dgc_batch_compress   K1 over all tensors, K3 for all thresholds, the selection
-                         chain with per-tensor state, one packed payload
+                         chain with per-tensor state, one packed payload (called as its
+                         halves dgc_batch_compress_begin[_ptrs]_clip — the clip, or
+                         ``_lib.NO_CLIP``, is K1's argument — and dgc_batch_compress_finish)
     one allgather        the packed payload, RCCL over xGMI (gloo stages via the host)
     decompress           zero fill + scatter over the flat output (``fill="auto"``/``"inline"``,
                          the default), or — opted in with ``fill="sparse"`` by a caller that
@@ -95,7 +97,7 @@ class DGCBatch(ReceiveSide):
         self.grad_flat = torch.zeros(self.flat_numel, dtype=dtype, device=dev)
         self._mmt_flat = torch.zeros(self.flat_numel, dtype=dtype, device=dev)
         self._vec_flat = torch.zeros(self.flat_numel, dtype=dtype, device=dev)
-        # 16-bit: K1-16 (dgc_compensate16) rounds every op to the dtype and writes the new
+        # 16-bit: K1-16 (dgc_compensate16_clip) rounds every op to the dtype and writes the new
         # velocity's exact fp32 image, which the selection reads (dgc_batch_select); the
         # 16-bit state is masked from the payload (dgc_mask_packed16)
         self._vec32 = torch.zeros(self.flat_numel, dtype=torch.float32, device=dev) if self.half else None
@@ -214,48 +216,39 @@ class DGCBatch(ReceiveSide):
         arr = (ctypes.c_int64 * len(starts))(*starts)
         self._starts_arr = arr
         L, st = self._L, _lib.stream_of(self.device)
+        T = len(self.names)
+        flat = (self.grad_flat.data_ptr(), self._mmt_flat.data_ptr(), self._vec_flat.data_ptr())
         if self.half:
             if grad_ptrs is not None:   # the 16-bit gradients into the flat buffer (2-B gather)
-                numels, offs = self._arrays16()
-                _lib.check(L.dgc_gather16(grad_ptrs, numels, offs, len(self.names), self.grad_flat.data_ptr(), st),
-                           "dgc_gather16")
-            if self.clip is not None:
-                T = len(self.names)
-                numels, offs = self._arrays16()
-                base = self.grad_flat.data_ptr()
-                flat_ptrs = (ctypes.c_void_p * T)(*[base + 2 * o for o in self.offsets])
-                self.clip_coefs = self.clip.table_coefs(flat_ptrs, numels, T, self.device, dtype=self.dtype)
-                _lib.check(L.dgc_compensate16_multi_clip(self.grad_flat.data_ptr(), self._mmt_flat.data_ptr(),
-                                                         self._vec_flat.data_ptr(), self._vec32.data_ptr(), numels,
-                                                         offs, T, self.flat_numel, self.momentum, int(self.nesterov),
-                                                         _lib.VD[self.dtype], self.clip.kind,
-                                                         _lib.ptr(self.clip_coefs), self.clip.param, st),
-                           "dgc_compensate16_multi_clip")
+                _lib.check(L.dgc_gather16(grad_ptrs, *self._arrays16(), T, flat[0], st), "dgc_gather16")
+            # two kernels, so two calls: the whole-buffer K1-16 (padding included) without a
+            # clip, the multi-tensor K1-16 (one coefficient per tensor) with one
+            if self.clip is None:
+                _lib.check(L.dgc_compensate16_clip(*flat, None, self._vec32.data_ptr(), self.flat_numel,
+                                                   self.momentum, int(self.nesterov), 1, _lib.VD[self.dtype],
+                                                   *_lib.NO_CLIP, st), "dgc_compensate16_clip")
                 return
-            _lib.check(L.dgc_compensate16(self.grad_flat.data_ptr(), self._mmt_flat.data_ptr(),
-                                          self._vec_flat.data_ptr(), None, self._vec32.data_ptr(), self.flat_numel,
-                                          self.momentum, int(self.nesterov), 1, _lib.VD[self.dtype], st),
-                       "dgc_compensate16")
+            numels, offs = self._arrays16()
+            flat_ptrs = (ctypes.c_void_p * T)(*[flat[0] + 2 * o for o in self.offsets])
+            self.clip_coefs = self.clip.table_coefs(flat_ptrs, numels, T, self.device, dtype=self.dtype)
+            _lib.check(L.dgc_compensate16_multi_clip(*flat, self._vec32.data_ptr(), numels, offs, T, self.flat_numel,
+                                                     self.momentum, int(self.nesterov), _lib.VD[self.dtype],
+                                                     self.clip.kind, _lib.ptr(self.clip_coefs), self.clip.param, st),
+                       "dgc_compensate16_multi_clip")
             return
+        clip = None
         if self.clip is not None:
-            T = len(self.names)
-            if grad_ptrs is None:
-                base = self.grad_flat.data_ptr()
-                grad_ptrs = (ctypes.c_void_p * T)(*[base + 4 * o for o in self.offsets])
+            if grad_ptrs is None:   # the statistics read a pointer table: grad_flat's tensors
+                grad_ptrs = (ctypes.c_void_p * T)(*[flat[0] + 4 * o for o in self.offsets])
             self.clip_coefs = self.clip.table_coefs(grad_ptrs, self._arrays[0], T, self.device)
-            _lib.check(L.dgc_batch_compress_begin_ptrs_clip(ctypes.byref(self.desc), grad_ptrs,
-                                                            self._mmt_flat.data_ptr(), self._vec_flat.data_ptr(), arr,
-                                                            self.clip.kind, _lib.ptr(self.clip_coefs), self.clip.param,
-                                                            self.ws.data_ptr(), self.ws.numel(), st),
-                       "dgc_batch_compress_begin_ptrs_clip")
-        elif grad_ptrs is None:
-            _lib.check(L.dgc_batch_compress_begin(ctypes.byref(self.desc), self.grad_flat.data_ptr(),
-                                                  self._mmt_flat.data_ptr(), self._vec_flat.data_ptr(), arr,
-                                                  self.ws.data_ptr(), self.ws.numel(), st), "dgc_batch_compress_begin")
+            clip = (self.clip.kind, self.clip_coefs, self.clip.param)
+        # an unclipped step from grad_flat keeps the flat form (no pointer table to read)
+        if grad_ptrs is None:
+            begin, src, what = L.dgc_batch_compress_begin_clip, flat[0], "dgc_batch_compress_begin_clip"
         else:
-            _lib.check(L.dgc_batch_compress_begin_ptrs(ctypes.byref(self.desc), grad_ptrs, self._mmt_flat.data_ptr(),
-                                                       self._vec_flat.data_ptr(), arr, self.ws.data_ptr(),
-                                                       self.ws.numel(), st), "dgc_batch_compress_begin_ptrs")
+            begin, src, what = L.dgc_batch_compress_begin_ptrs_clip, grad_ptrs, "dgc_batch_compress_begin_ptrs_clip"
+        _lib.check(begin(ctypes.byref(self.desc), src, flat[1], flat[2], arr, *_lib.clip_args(clip),
+                         self.ws.data_ptr(), self.ws.numel(), st), what)
         self._pending = False
 
     def select(self):
@@ -315,10 +308,7 @@ class DGCBatch(ReceiveSide):
         indices relative to the tensor — what the reference's compress returns."""
         p = self.payload if rank_payload is None else rank_payload
         total = int(p[:8].view(torch.int64).item())
-        vb = torch.empty(0, dtype=self.vdtype).element_size()
-        ib = torch.empty(0, dtype=self.idtype).element_size()
-        vals = p[self.voff: self.voff + total * vb].view(self.vdtype)
-        idxs = p[self.ioff: self.ioff + total * ib].view(self.idtype)
+        vals, idxs = _lib.payload_views(p, self.voff, self.ioff, self.vdtype, self.idtype, total)
         counts = [i["count"] for i in self.infos()]
         res, pos = {}, 0
         for name, off, c in zip(self.names, self.offsets, counts):

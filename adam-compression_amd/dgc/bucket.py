@@ -27,7 +27,7 @@ every decision kept on the device:
 
 ``dtype=torch.bfloat16`` / ``torch.float16``: momentum, velocity, gradient and output are
 16-bit, every op of the reference rounded to the dtype as on the per-tensor path. K1-16
-(``dgc_compress_begin16``) streams the 16-bit state, writes the new velocity's exact fp32
+(``dgc_compress_begin16_clip``) streams the 16-bit state, writes the new velocity's exact fp32
 image and takes the samples and the candidate lists from it; the selection then runs
 pure on the image and the 16-bit state is masked from the payload
 (``dgc_mask_packed16``), so nothing is ever deferred. The receive side is the 16-bit
@@ -36,17 +36,16 @@ packed decompress (``dgc_decompress_packed16``: dense fill, one exchange part).
 ``clip=``: the reference's local gradient clipping (a ``dgc.clip_grad.ClipSpec``, or one of
 ``clip_grad_norm_`` (norm 2 / inf) / ``clip_grad_value_``, bare or as a ``functools.partial``)
 fused into K1's load of the gradient: the bucket's statistic (``dgc_grad_stats`` /
-``dgc_grad_stats16``), the coefficient (``dgc_clip_coefs`` / ``dgc_clip_coefs16``), then
-``dgc_compress_begin_clip`` / ``dgc_compress_begin16_clip`` — stream-ordered, nothing read
-back; ``clip_coef`` holds the device coefficient of the last step. The gradient stays as
-it was.
+``dgc_grad_stats16``), the coefficient (``dgc_clip_coefs`` / ``dgc_clip_coefs16``), then K1's
+one call per precision, ``dgc_compress_begin_clip`` / ``dgc_compress_begin16_clip``, with
+them (``_lib.NO_CLIP`` without a clip) — stream-ordered, nothing read back; ``clip_coef``
+holds the device coefficient of the last step. The gradient stays as it was.
 
 The numerics are those of the drop-in ``DGCCompressor`` + ``DGCSGDMemory`` (same
 kernels); the sample start is drawn from a ``random.Random`` seeded identically on
 every rank, one draw per step, like the reference's global ``random`` call.
 """
 import ctypes
-import math
 import random
 
 import torch
@@ -108,27 +107,21 @@ class DGCBucket(ReceiveSide):
         self.idtype = torch.int32 if int32_indices else torch.int64
         self.rng = random.Random(seed)
 
-        p = _lib.SelectParams()
-        p.numel, p.num_selects, p.num_samples = N, self.k, self.num_samples
-        p.upper_count = math.floor(self.k * compress_upper_bound)
-        p.lower_count = math.ceil(compress_lower_bound * self.k)
-        p.upper, p.lower = float(compress_upper_bound), float(compress_lower_bound)
-        p.max_iters, p.resample, p.masking = int(max_adaptation_iters), int(bool(resample)), int(bool(momentum_masking))
+        self.status = _lib.StatusSink("DGCBucket", self.device)   # DGC_K5_BROKEN, checked every step
         # update_memory 2: the first-k branches' DGCSGDMemory.update zeroing rides in the
-        # next step's K1, which streams vec/mmt anyway (mmt/vec below flush it on read)
-        p.vdtype, p.idtype = _lib.VD[self.vdtype], _lib.ID[self.idtype]
-        p.update_memory = 2 if deferred_masking else 1
+        # next step's K1, which streams vec/mmt anyway (mmt/vec below flush it on read).
+        # resample_order "index" (opt-in): an untied resample lists its set in index order
+        # (DGCBatch's default); a flat bucket's resample (up to 64k candidates) mostly exceeds
+        # the one-workgroup set path, so it keeps torch.topk's order by default
+        p = _lib.select_params(N, self.k, self.num_samples, compress_upper_bound, compress_lower_bound,
+                               max_adaptation_iters, resample, momentum_masking, 2 if deferred_masking else 1,
+                               self.vdtype, self.idtype, resample_order=resample_order,
+                               status_sink=self.status.address)
         if self.half:
             # the selection runs pure on the fp32 image (update_memory 0; with masking set and
             # no momentum dgc_compress_finish writes nothing), its threshold *= bound products
             # rounded to the dtype; momentum_masking decides what dgc_mask_packed16 masks
             p.update_memory, p.masking, p.thr_dtype = 0, 1, _lib.VD[dtype]
-        # "index" (opt-in): an untied resample lists its set in index order (DGCBatch's
-        # default); a flat bucket's resample (up to 64k candidates) mostly exceeds the
-        # one-workgroup set path, so it keeps torch.topk's order by default
-        p.resample_order = _lib.resample_order_flag(resample_order)
-        self.status = _lib.StatusSink("DGCBucket", self.device)   # DGC_K5_BROKEN, checked every step
-        p.status_sink = self.status.address
         self.params = p
 
         dev = self.device
@@ -194,37 +187,24 @@ class DGCBucket(ReceiveSide):
                     and grad.numel() == self.numel and grad.data_ptr() % 16 == 0):
                 raise ValueError(f"DGCBucket.compensate: grad must be a contiguous, 16-B aligned {self.dtype} CUDA "
                                  f"tensor of {self.numel} elements")
-            if self.clip is not None:
-                self.clip_coef = self.clip.table_coefs((ctypes.c_void_p * 1)(grad.data_ptr()), self._clip_numel, 1,
-                                                       self.device, dtype=self.dtype)
-                _lib.check(L.dgc_compress_begin16_clip(grad.data_ptr(), self._mmt.data_ptr(), self._vec.data_ptr(),
-                                                       self._vec32.data_ptr(), self.momentum, int(self.nesterov),
-                                                       self.start, self.stride, ctypes.byref(self.params),
-                                                       self.spec.data_ptr(), self.clip.kind, _lib.ptr(self.clip_coef),
-                                                       self.clip.param, self.ws.data_ptr(), self.ws.numel(),
-                                                       _lib.VD[self.dtype], _lib.stream_of(self.device)),
-                           "dgc_compress_begin16_clip")
-                return
-            _lib.check(L.dgc_compress_begin16(grad.data_ptr(), self._mmt.data_ptr(), self._vec.data_ptr(),
-                                              self._vec32.data_ptr(), self.momentum, int(self.nesterov), self.start,
-                                              self.stride, ctypes.byref(self.params), self.spec.data_ptr(),
-                                              self.ws.data_ptr(), self.ws.numel(), _lib.VD[self.dtype],
-                                              _lib.stream_of(self.device)), "dgc_compress_begin16")
-            return
-        if self.clip is not None:
+        clip = None
+        if self.clip is not None:   # the bucket's statistic and coefficient, then the clip in K1's load
             self.clip_coef = self.clip.table_coefs((ctypes.c_void_p * 1)(grad.data_ptr()), self._clip_numel, 1,
-                                                   self.device)
-            _lib.check(L.dgc_compress_begin_clip(grad.data_ptr(), self._mmt.data_ptr(), self._vec.data_ptr(),
-                                                 self.momentum, int(self.nesterov), self.start, self.stride,
-                                                 ctypes.byref(self.params), self.spec.data_ptr(), self.clip.kind,
-                                                 _lib.ptr(self.clip_coef), self.clip.param, self.ws.data_ptr(),
-                                                 self.ws.numel(), _lib.stream_of(self.device)),
-                       "dgc_compress_begin_clip")
-        else:
-            _lib.check(L.dgc_compress_begin(grad.data_ptr(), self._mmt.data_ptr(), self._vec.data_ptr(),
-                                            self.momentum, int(self.nesterov), self.start, self.stride,
-                                            ctypes.byref(self.params), self.spec.data_ptr(), self.ws.data_ptr(),
-                                            self.ws.numel(), _lib.stream_of(self.device)), "dgc_compress_begin")
+                                                   self.device, dtype=self.dtype)
+            clip = (self.clip.kind, self.clip_coef, self.clip.param)
+        st = _lib.stream_of(self.device)
+        if self.half:
+            _lib.check(L.dgc_compress_begin16_clip(grad.data_ptr(), self._mmt.data_ptr(), self._vec.data_ptr(),
+                                                   self._vec32.data_ptr(), self.momentum, int(self.nesterov),
+                                                   self.start, self.stride, ctypes.byref(self.params),
+                                                   self.spec.data_ptr(), *_lib.clip_args(clip), self.ws.data_ptr(),
+                                                   self.ws.numel(), _lib.VD[self.dtype], st),
+                       "dgc_compress_begin16_clip")
+            return
+        _lib.check(L.dgc_compress_begin_clip(grad.data_ptr(), self._mmt.data_ptr(), self._vec.data_ptr(),
+                                             self.momentum, int(self.nesterov), self.start, self.stride,
+                                             ctypes.byref(self.params), self.spec.data_ptr(), *_lib.clip_args(clip),
+                                             self.ws.data_ptr(), self.ws.numel(), st), "dgc_compress_begin_clip")
         self._pending = False   # K1 applied it
 
     def select(self):

@@ -50,6 +50,11 @@ COEF_NORM, COEF_GLOBAL_VALUE, COEF_GLOBAL_NORM2 = 0, 1, 2
 CLIP_NONE, CLIP_SCALE, CLIP_CLAMP = 0, 1, 2
 
 
+def _table1(g):
+    """The one-entry (pointers, numels) table of the tensor ``g``."""
+    return (ctypes.c_void_p * 1)(g.data_ptr()), (ctypes.c_int64 * 1)(g.numel())
+
+
 class ClipSpec:
     """What a clipping callable does: ``mode`` ("norm2", "norminf", "normp", "value",
     "global_value", "global_norm2"), its parameter (``max_norm`` or ``clip_value``;
@@ -136,16 +141,10 @@ class ClipSpec:
         the fixed clamp); of a bf16 / fp16 tensor for a local clip."""
         if self.mode == "value":
             return None
-        if g.dtype in _lib.HALF:
-            ptrs = (ctypes.c_void_p * 1)(g.data_ptr())
-            numels = (ctypes.c_int64 * 1)(g.numel())
-            return self.table_coefs(ptrs, numels, 1, g.device, dtype=g.dtype)
-        if self.mode == "normp":
+        if self.mode == "normp" and g.dtype == torch.float32:
             stats = g.norm(self.norm_type).reshape(1)
             return self.coefs_of(stats, 1)
-        ptrs = (ctypes.c_void_p * 1)(g.data_ptr())
-        numels = (ctypes.c_int64 * 1)(g.numel())
-        return self.table_coefs(ptrs, numels, 1, g.device)
+        return self.table_coefs(*_table1(g), 1, g.device, dtype=g.dtype)
 
     def apply_(self, grad):
         """The clip in place on ``grad.data``; returns ``grad``."""
@@ -156,11 +155,8 @@ class ClipSpec:
         if data.dtype in _lib.HALF:
             return self._apply16_(grad)
         g = data if data.is_contiguous() else data.contiguous()
-        _lib.require_cuda_f32(g, "dgc.clip_grad")
-        c = self.coef(g)
-        ptrs = (ctypes.c_void_p * 1)(g.data_ptr())
-        numels = (ctypes.c_int64 * 1)(g.numel())
-        _lib.check(_lib.lib().dgc_clip_apply(ptrs, numels, 1, self.kind, _lib.ptr(c), self.param,
+        _lib.require_cuda_float(g, "dgc.clip_grad", dtypes=(torch.float32,))
+        _lib.check(_lib.lib().dgc_clip_apply(*_table1(g), 1, self.kind, _lib.ptr(self.coef(g)), self.param,
                                              _lib.stream_of(g.device)), "dgc_clip_apply")
         if g is not data:
             data.copy_(g)

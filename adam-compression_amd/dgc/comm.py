@@ -143,7 +143,7 @@ def allreduce_async_(tensor, name=None, op=Average):
             from . import _lib
             g = gathered.to(src.device) if not gathered.is_cuda else gathered
             dst = src if src.data_ptr() == tensor.data_ptr() else torch.empty_like(src)
-            _lib.check(_lib.lib().dgc_rank_sum(_lib.ptr(g), _lib.VD[src.dtype], W, n * src.element_size(), n,
+            _lib.check(_lib.lib().dgc_rank_sum(_lib.ptr(g), _lib.VD[src.dtype], W, n * _lib.itemsize(src.dtype), n,
                                                int(op == Average), _lib.ptr(dst), _lib.stream_of(src.device)),
                        "dgc_rank_sum")
             if dst.data_ptr() != tensor.data_ptr():

@@ -6,10 +6,12 @@
 Python-global ``random.randint`` draw of the sample start at the same call point
 (dgc/compression.py:118). All tensor work runs in ``libdgc_hip.so`` on the MI355X:
 
-  compress    ``dgc_compress``: K1 compensate with the strided sample fused in,
-              K3 radix-select threshold, K4 select / adaptation loop / resample /
-              pack / momentum masking. One host synchronisation per call, to
-              return exact-length ``[n, 1]`` tensors as the reference does.
+  compress    ``dgc_compress``, or with a ``dgc.clip_grad`` clip the memory fuses its
+              two halves ``dgc_compress_begin_clip`` (the clip is K1's argument) +
+              ``dgc_compress_finish``: K1 compensate with the strided sample fused
+              in, K3 radix-select threshold, K4 select / adaptation loop / resample /
+              pack / momentum masking. One host synchronisation per call, to return
+              exact-length ``[n, 1]`` tensors as the reference does.
   communicate one RCCL ``all_gather_into_tensor`` of the packed per-rank payload
               ``[count | values | indices]`` (fixed capacity = num_selects).
   decompress  ``dgc_decompress(_packed)``: deterministic rank-order scatter-add.
@@ -17,6 +19,7 @@ Python-global ``random.randint`` draw of the sample start at the same call point
 Wire casts follow the reference (fp16 values, int32 indices). int32 indices are
 refused for tensors above 2^31 - 1 elements, where the reference's cast wraps.
 """
+import ctypes
 import math
 import random
 
@@ -198,20 +201,10 @@ class DGCCompressor:
         p = self._params.get(key)
         if p is None:
             numel, _, k, S, _, _ = self.attributes[name]
-            p = _lib.SelectParams()
-            p.numel, p.num_selects, p.num_samples = numel, k, S
-            # n > k * upper  and  n < lower * k compare an int with a Python double
-            p.upper_count = math.floor(k * self.compress_upper_bound)
-            p.lower_count = math.ceil(self.compress_lower_bound * k)
-            p.upper, p.lower = float(self.compress_upper_bound), float(self.compress_lower_bound)
-            p.max_iters = int(self.max_adaptation_iters)
-            p.resample = int(bool(self.resample))
-            p.masking = int(bool(masking))
-            p.vdtype = _lib.VD[torch.float16 if self.fp16_values else dtype]
-            p.thr_dtype = _lib.VD[dtype]   # threshold *= bound rounds to the tensor's dtype
-            p.idtype = _lib.ID[torch.int32 if self.int32_indices else torch.int64]
-            p.update_memory = int(bool(update_memory))
-            self._params[key] = p
+            p = self._params[key] = _lib.select_params(
+                numel, k, S, self.compress_upper_bound, self.compress_lower_bound, self.max_adaptation_iters,
+                self.resample, masking, bool(update_memory), torch.float16 if self.fp16_values else dtype,
+                torch.int32 if self.int32_indices else torch.int64, thr_dtype=dtype)
         return p
 
     def _new_payload(self, name, device, dtype=torch.float32):
@@ -224,10 +217,8 @@ class DGCCompressor:
 
     def _views(self, payload, lay, n):
         k, vdt, idt, stride, voff, ioff = lay
-        vb, ib = torch.empty(0, dtype=vdt).element_size(), torch.empty(0, dtype=idt).element_size()
-        values = payload[voff: voff + n * vb].view(vdt).view(-1, 1)
-        indices = payload[ioff: ioff + n * ib].view(idt).view(-1, 1)
-        return values, indices
+        values, indices = _lib.payload_views(payload, voff, ioff, vdt, idt, n)
+        return values.view(-1, 1), indices.view(-1, 1)
 
     def _sample_start(self, name):
         numel, _, _, S, _, stride = self.attributes[name]
@@ -304,27 +295,29 @@ class DGCCompressor:
             dev = tensor.device
             dt = _lib.require_cuda_float(tensor, "DGCCompressor.compress", contiguous=False)
             payload, lay = self._new_payload(name, dev, dt)
-            if isinstance(mem, DGCSGDMemory) and dt in _lib.HALF:
+            half = dt in _lib.HALF
+            native = isinstance(mem, DGCSGDMemory) and (half or self.strided_sample)
+            if native:
+                # a dgc.clip_grad function the memory can fuse: stats -> coefs here, then the
+                # clip as K1 / K1-16 loads the gradient; any other callable is called first
+                clip = mem.fused_clip(tensor.reshape(-1)) if tensor.is_contiguous() else None
+                grad = (tensor if clip is not None else mem._clip(tensor)).reshape(-1)
+                if half:
+                    grad = grad.contiguous()
+                else:
+                    _lib.require_cuda_float(grad, "DGCCompressor.compress", dtypes=(torch.float32,))
+                mem._sync()
+                mmt, vec = mem.state_of(name, grad, True, "DGCCompressor.compress")
+            if native and half:
                 # 16-bit state: K1-16 writes the velocity's fp32 image, the selection runs
                 # on it (pure), then DGCSGDMemory.update masks the 16-bit state
-                # a local dgc.clip_grad function: stats -> coefs, then the clip in K1-16's load
-                fused_clip = mem.fused_clip(tensor.reshape(-1)) if tensor.is_contiguous() else None
-                grad = (tensor if fused_clip is not None else mem._clip(tensor)).reshape(-1).contiguous()
-                mem._sync()
-                mem.state_of(name, grad, True, "DGCCompressor.compress")
                 img = self._ws.get(dev, 4 * numel, "img16")[: 4 * numel].view(torch.float32)
-                mem._compensate16(grad, name, True, vec32=img, clip=fused_clip)
+                mem._k1(grad, name, True, vec32=img, clip=clip)
                 _, idx, _, _, _ = self._select_on(img, name, dt, payload, lay, False)
                 mem.update(name, (idx,))
                 values, indices = self._views(payload, lay, idx.numel())
-            elif isinstance(mem, DGCSGDMemory) and self.strided_sample:
-                # fused path: K1 (+sample) -> K3 -> K4 (+update) in one library call
-                # a dgc.clip_grad function: stats -> coefs, then the clip in K1's registers
-                fused_clip = mem.fused_clip(tensor.reshape(-1)) if tensor.is_contiguous() else None
-                grad = (tensor if fused_clip is not None else mem._clip(tensor)).reshape(-1)
-                _lib.require_cuda_f32(grad, "DGCCompressor.compress")
-                mem._sync()
-                mmt, vec = mem.state_of(name, grad, True, "DGCCompressor.compress")
+            elif native:
+                # fused path: K1 (+sample, + lists) then K3 -> K4 (+update)
                 start = self._sample_start(name)
                 params = self._select_params(name, mem.momentum_masking, True)
                 L = _lib.lib()
@@ -336,21 +329,21 @@ class DGCCompressor:
                 info = torch.empty(_lib.INFO_BYTES, dtype=torch.uint8, device=dev)
                 base = payload.data_ptr()
                 voff, ioff = lay[4], lay[5]
-                if fused_clip is None:
-                    _lib.check(L.dgc_compress(_lib.ptr(grad), _lib.ptr(mmt), _lib.ptr(vec), float(mem.momentum),
-                                              int(bool(mem.nesterov)), start, stride, ks, params, _lib.ptr(spec),
-                                              _lib.SPEC_MARGIN, base + voff, base + ioff, base, _lib.ptr(info),
-                                              _lib.ptr(ws), wsz, _lib.SYNC_HOST, _lib.stream_of(dev)), "dgc_compress")
+                st = _lib.stream_of(dev)
+                k1 = (_lib.ptr(grad), _lib.ptr(mmt), _lib.ptr(vec), float(mem.momentum), int(bool(mem.nesterov)),
+                      start, stride)
+                rest = (params, _lib.ptr(spec), _lib.SPEC_MARGIN, base + voff, base + ioff, base, _lib.ptr(info),
+                        _lib.ptr(ws), wsz, _lib.SYNC_HOST, st)
+                if clip is None:
+                    # dgc_compress is begin + finish in one call. Every other K1 of the package
+                    # goes through its _clip entry; here the second ctypes call per tensor cost
+                    # 5 % of a per-tensor ResNet-50 step, so the unclipped case
+                    # keeps the single call
+                    _lib.check(L.dgc_compress(*k1, ks, *rest), "dgc_compress")
                 else:
-                    kind, coef, value = fused_clip
-                    st = _lib.stream_of(dev)
-                    _lib.check(L.dgc_compress_begin_clip(_lib.ptr(grad), _lib.ptr(mmt), _lib.ptr(vec),
-                                                         float(mem.momentum), int(bool(mem.nesterov)), start, stride,
-                                                         params, _lib.ptr(spec), kind, _lib.ptr(coef), value,
+                    _lib.check(L.dgc_compress_begin_clip(*k1, params, _lib.ptr(spec), *_lib.clip_args(clip),
                                                          _lib.ptr(ws), wsz, st), "dgc_compress_begin_clip")
-                    _lib.check(L.dgc_compress_finish(_lib.ptr(vec), _lib.ptr(mmt), start, stride, ks, params,
-                                                     _lib.ptr(spec), _lib.SPEC_MARGIN, base + voff, base + ioff, base,
-                                                     _lib.ptr(info), _lib.ptr(ws), wsz, _lib.SYNC_HOST, st),
+                    _lib.check(L.dgc_compress_finish(_lib.ptr(vec), _lib.ptr(mmt), start, stride, ks, *rest),
                                "dgc_compress_finish")
                 n = self._count(info)
                 values, indices = self._views(payload, lay, n)
@@ -408,17 +401,10 @@ class DGCCompressor:
                                                    idd, _lib.ptr(grad), numel, scale, _lib.ptr(ws), wsz,
                                                    stream), "dgc_decompress_packed")
                 return grad.view(shape)
-            values, indices = tensor
-            values = values.reshape(-1).contiguous()
-            indices = indices.reshape(-1).contiguous()
-            if values.dtype not in _lib.VD:
-                values = values.to(torch.float32)
-            if indices.dtype not in _lib.ID:
-                indices = indices.to(torch.int64)
+            values, indices = self._wire(tensor, torch.float32)
             # index_put_ wraps a negative index (>= -numel); the kernels take [0, numel)
             indices = torch.where(indices < 0, indices + numel, indices)
             offs = getattr(tensor, "run_offsets", None)
-            import ctypes
             if offs is not None:
                 arr = (ctypes.c_int64 * len(offs))(*offs)
                 nruns = len(offs) - 1
@@ -443,17 +429,23 @@ class DGCCompressor:
             tensor = tensor.type(vdtype)
         return self.memory.compensate(tensor, name, accumulate=False)
 
-    def _decompress16(self, tensor, grad, numel, shape, scale):
-        """dgc/compression.py:179-194 into a bf16 / fp16 gradient (dgc_decompress16):
-        runs (ranks) in rank order, every add and the 1/W scale rounded to its dtype."""
-        import ctypes
+    @staticmethod
+    def _wire(tensor, vdtype):
+        """decompress's (values, indices) as flat contiguous tensors of dtypes the kernels
+        read (anything else: values cast to ``vdtype``, indices to int64)."""
         values, indices = tensor
         values = values.reshape(-1).contiguous()
         indices = indices.reshape(-1).contiguous()
         if values.dtype not in _lib.VD:
-            values = values.to(grad.dtype)
+            values = values.to(vdtype)
         if indices.dtype not in _lib.ID:
             indices = indices.to(torch.int64)
+        return values, indices
+
+    def _decompress16(self, tensor, grad, numel, shape, scale):
+        """dgc/compression.py:179-194 into a bf16 / fp16 gradient (dgc_decompress16):
+        runs (ranks) in rank order, every add and the 1/W scale rounded to its dtype."""
+        values, indices = self._wire(tensor, grad.dtype)
         offs = getattr(tensor, "run_offsets", None)
         if offs is None or not getattr(tensor, "distinct_runs", False):
             # input whose runs may repeat an index (the reference's list format, or
@@ -517,10 +509,8 @@ class DGCCompressor:
                 raise RuntimeError(f"DGCCompressor.synchronize: {handle.name}: the payload gathered from rank(s) {bad} "
                                    f"holds count(s) {[counts[r] for r in bad]} outside [0, {handle.capacity}] "
                                    "(corrupted in transit?)")
-            vb = torch.empty(0, dtype=handle.vdtype).element_size()
-            ib = torch.empty(0, dtype=handle.idtype).element_size()
-            vals = [rows[r, handle.voff: handle.voff + c * vb].view(handle.vdtype) for r, c in enumerate(counts)]
-            idxs = [rows[r, handle.ioff: handle.ioff + c * ib].view(handle.idtype) for r, c in enumerate(counts)]
+            vals, idxs = zip(*[_lib.payload_views(rows[r], handle.voff, handle.ioff, handle.vdtype, handle.idtype, c)
+                               for r, c in enumerate(counts)])
             out = _Gathered([torch.cat(vals).view(-1, 1), torch.cat(idxs).view(-1, 1)])
             out.packed = gathered
             out.world = W

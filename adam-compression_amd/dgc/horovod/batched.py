@@ -164,7 +164,7 @@ class BatchedStep:
         # payload's tail, summed in rank order after the ONE allgather (dgc_compensate_ranks)
         exchanging = comm.size() > 1 or comm.one_rank_collectives()
         wire_dt = torch.float16 if c.fp16_values else torch.float32
-        dense_bytes = end * torch.empty(0, dtype=wire_dt).element_size() if dense and exchanging and not self.half else 0
+        dense_bytes = end * _lib.itemsize(wire_dt) if dense and exchanging and not self.half else 0
         if comp_names:
             shapes = [(n, tuple(params[n].shape)) for n in comp_names]
             b = DGCBatch(shapes, compress_ratio=c.compress_ratio, momentum=mem.momentum, nesterov=mem.nesterov,
@@ -328,9 +328,9 @@ class BatchedStep:
                 src = plan["dense_in"]
                 if dense_handle is not None:   # decompress: tensor.type(vdtype) (dgc/compression.py:196-197)
                     src = comm.synchronize(dense_handle).to(self.dtype)
-                _lib.check(L.dgc_compensate16(_lib.ptr(src), _lib.ptr(mmt), None, _lib.ptr(out), None,
-                                              plan["dense_numel"], float(mem.momentum), int(bool(mem.nesterov)), 0,
-                                              _lib.VD[self.dtype], st), "dgc_compensate16")
+                _lib.check(L.dgc_compensate16_clip(_lib.ptr(src), _lib.ptr(mmt), None, _lib.ptr(out), None,
+                                                   plan["dense_numel"], float(mem.momentum), int(bool(mem.nesterov)),
+                                                   0, _lib.VD[self.dtype], *_lib.NO_CLIP, st), "dgc_compensate16_clip")
             elif "wire_dtype" in plan:
                 # Average = the rank-order sum / W of the gathered wire values, then
                 # compensate(accumulate=False) (dgc/compression.py:195-198, 205-206)
@@ -351,30 +351,27 @@ class BatchedStep:
                     if avg32 is not avg:   # decompress: tensor.type(vdtype) (dgc/compression.py:196-197)
                         _lib.check(L.dgc_widen16(_lib.ptr(avg), _lib.ptr(avg32), plan["dense_numel"], wd, st),
                                    "dgc_widen16")
-                    self._dense_clipped(plan, plan["dense_avg_ptrs"], torch.float32, L, st)
+                    self._dense_multi(plan, plan["dense_avg_ptrs"], torch.float32, L, st)
             else:   # one rank: the allreduce is the identity, the fp16 wire a rounding
-                rnd = torch.float16 if self.comp.fp16_values else torch.float32
-                if self.clip is None:
-                    _lib.check(L.dgc_compensate_multi(plan["dense_ptrs"], plan["dense_numels"], plan["dense_offs"],
-                                                      len(plan["dense"]), _lib.VD[rnd], _lib.ptr(mmt), _lib.ptr(out),
-                                                      float(mem.momentum), int(bool(mem.nesterov)), st),
-                               "dgc_compensate_multi")
-                else:
-                    self._dense_clipped(plan, plan["dense_ptrs"], rnd, L, st)
+                self._dense_multi(plan, plan["dense_ptrs"], torch.float16 if self.comp.fp16_values else torch.float32,
+                                  L, st)
             # p.grad.set_(compensate(accumulate=False)) (dgc/compression.py:195-198)
             glue.bind_grads(plan["dense_params"], plan["dense_views"])
             plan.pop("keep", None)
 
-    def _dense_clipped(self, plan, ptrs, round_to, L, st):
-        """compensate(accumulate=False) of the dense tensors at ``ptrs`` with the clip fused:
-        their statistics (of the values K1 sees: ``round_to``), the coefficients, K1."""
-        mem, T = self.mem, len(plan["dense"])
-        coefs = self.clip.table_coefs(ptrs, plan["dense_numels"], T, plan["dev"], round_to)
-        plan["dense_clip_coefs"] = coefs
+    def _dense_multi(self, plan, ptrs, round_to, L, st):
+        """compensate(accumulate=False) of the dense tensors at ``ptrs``, rounded to
+        ``round_to`` as they are loaded; with a clip, fused: their statistics (of the values
+        K1 sees), the coefficients, K1."""
+        mem, T, clip = self.mem, len(plan["dense"]), None
+        if self.clip is not None:
+            coefs = plan["dense_clip_coefs"] = self.clip.table_coefs(ptrs, plan["dense_numels"], T, plan["dev"],
+                                                                     round_to)
+            clip = (self.clip.kind, coefs, self.clip.param)
         _lib.check(L.dgc_compensate_multi_clip(ptrs, plan["dense_numels"], plan["dense_offs"], T, _lib.VD[round_to],
                                                _lib.ptr(plan["dense_mmt"]), _lib.ptr(plan["dense_out"]),
-                                               float(mem.momentum), int(bool(mem.nesterov)), self.clip.kind,
-                                               _lib.ptr(coefs), self.clip.param, st), "dgc_compensate_multi_clip")
+                                               float(mem.momentum), int(bool(mem.nesterov)), *_lib.clip_args(clip),
+                                               st), "dgc_compensate_multi_clip")
 
     def _dense16_exchange(self, plan, L, st):
         """16-bit dense tensors: the gradients gathered into one buffer (2-B copies),

@@ -4,8 +4,9 @@ Same classes, constructor arguments, methods and state layout as the reference
 (``Memory`` static API, dgc/memory.py:9-28; ``DGCSGDMemory``, dgc/memory.py:31-88).
 The arithmetic runs in ``libdgc_hip.so`` on the MI355X:
 
-* ``compensate``  -> ``dgc_compensate`` (K1: one fused streaming pass, fp32 with the
-  reference's two separate roundings, no FMA contraction);
+* ``compensate``  -> ``dgc_compensate_clip`` (K1: one fused streaming pass, fp32 with the
+  reference's two separate roundings, no FMA contraction; the clip is an argument,
+  ``_lib.NO_CLIP`` without one);
 * ``update``      -> ``dgc_mask_indices`` (the same masking that ``dgc_compress``
   fuses into its emit kernel when the compressor drives this memory);
 * ``gradient_clipping`` -> when it is one of ``dgc.clip_grad``'s functions (or a
@@ -18,7 +19,7 @@ The arithmetic runs in ``libdgc_hip.so`` on the MI355X:
 
 ``momentums`` / ``velocities`` stay plain param-shaped tensors of the parameter's dtype
 keyed by name, so ``state_dict`` / ``load_state_dict`` and checkpoints are unchanged.
-bf16 / fp16 parameters run ``dgc_compensate16`` / ``dgc_mask_indices16``: every op of
+bf16 / fp16 parameters run ``dgc_compensate16_clip`` / ``dgc_mask_indices16``: every op of
 the reference rounds to the dtype, as ATen does on a 16-bit tensor.
 """
 import ctypes
@@ -110,20 +111,21 @@ class DGCSGDMemory(Memory):
         return self._clip_spec[1]
 
     def fused_clip(self, grad):
-        """(clip kind, device coefficient or None, clamp value) for K1 when the clip of
-        ``grad`` (contiguous) can be fused: a recognised spec on an fp32 device tensor, or a
-        local one on a bf16 / fp16 device tensor (``ClipSpec.fusable``). The statistic and
-        the coefficient are issued here, stream-ordered; None otherwise."""
-        if not self._fusable(grad):
-            return None
-        spec = self.clip_spec()
-        _lib.require_cuda_float(grad, "DGCSGDMemory.gradient_clipping")
-        coef = self.last_clip_coef = spec.coef(grad)
-        return spec.kind, coef, spec.param
+        """(clip kind, device coefficient or None, clamp value) for K1 (``_lib.clip_args``) when
+        the clip of ``grad`` (contiguous) can be fused: a recognised spec on an fp32 device
+        tensor, or a local one on a bf16 / fp16 device tensor (``ClipSpec.fusable``). The
+        statistic and the coefficient are issued here, stream-ordered; None otherwise."""
+        return self._issue_clip(grad) if self._fusable(grad) else None
 
     def _fusable(self, grad):
         spec = self.clip_spec()
         return spec is not None and torch.is_tensor(grad) and grad.is_cuda and spec.fusable(grad.dtype)
+
+    def _issue_clip(self, grad):
+        spec = self.clip_spec()
+        _lib.require_cuda_float(grad, "DGCSGDMemory.gradient_clipping")
+        coef = self.last_clip_coef = spec.coef(grad)
+        return spec.kind, coef, spec.param
 
     def state_of(self, name, like, accumulate=True, what="DGCSGDMemory.compensate"):
         """(momentum, velocity or None) of ``name``, checked before their pointers reach a
@@ -152,43 +154,27 @@ class DGCSGDMemory(Memory):
         accumulate=False (dense tensors) returns a new tensor."""
         self._sync()
         fusable = self._fusable(grad)
-        if not fusable:
-            grad = self._clip(grad)
-        g = grad.contiguous()
-        dt = _lib.require_cuda_float(g, "DGCSGDMemory.compensate")
-        mmt, _ = self.state_of(name, g, accumulate)
-        L = _lib.lib()
-        stream = _lib.stream_of(g.device)
-        if dt in _lib.HALF:
-            return self._compensate16(g, name, accumulate, clip=self.fused_clip(g) if fusable else None)
-        vec = self.velocities[name] if accumulate else None
-        out = None if accumulate else torch.empty_like(mmt)
-        args = (_lib.ptr(g), _lib.ptr(mmt), _lib.ptr(vec), _lib.ptr(out), mmt.numel(), float(self.momentum),
-                int(bool(self.nesterov)), int(accumulate), None, 0, 1, 0)
-        if fusable:
-            kind, coef, value = self.fused_clip(g)
-            _lib.check(L.dgc_compensate_clip(*args, kind, _lib.ptr(coef), value, stream), "dgc_compensate_clip")
-        else:
-            _lib.check(L.dgc_compensate(*args, stream), "dgc_compensate")
-        return vec if accumulate else out
+        g = (grad if fusable else self._clip(grad)).contiguous()
+        _lib.require_cuda_float(g, "DGCSGDMemory.compensate")
+        return self._k1(g, name, accumulate, clip=self._issue_clip(g) if fusable else None)
 
-    def _compensate16(self, g, name, accumulate, vec32=None, clip=None):
-        """compensate on a bf16 / fp16 state (K1-16); vec32: optional fp32 image of the
-        new velocity for the selection (the compressor's fused path); clip: ``fused_clip``'s
-        result, applied as K1-16 loads the gradient."""
-        mmt, _ = self.state_of(name, g, accumulate)
-        L = _lib.lib()
-        dt = _lib.VD[g.dtype]
-        stream = _lib.stream_of(g.device)
-        vec = self.velocities[name] if accumulate else None
+    def _k1(self, g, name, accumulate, vec32=None, clip=None):
+        """K1 / K1-16 on the contiguous device gradient ``g``, by its dtype; clip:
+        ``fused_clip``'s result, applied as the gradient is loaded (None: unclipped); vec32
+        (16-bit state only): optional fp32 image of the new velocity for the selection
+        (the compressor's 16-bit branch)."""
+        mmt, vec = self.state_of(name, g, accumulate)
         out = None if accumulate else torch.empty_like(mmt)
-        args = (_lib.ptr(g), _lib.ptr(mmt), _lib.ptr(vec), _lib.ptr(out), _lib.ptr(vec32) if accumulate else None,
-                mmt.numel(), float(self.momentum), int(bool(self.nesterov)), int(accumulate), dt)
-        if clip is None:
-            _lib.check(L.dgc_compensate16(*args, stream), "dgc_compensate16")
-        else:
-            kind, coef, value = clip
-            _lib.check(L.dgc_compensate16_clip(*args, kind, _lib.ptr(coef), value, stream), "dgc_compensate16_clip")
+        L = _lib.lib()
+        head = (_lib.ptr(g), _lib.ptr(mmt), _lib.ptr(vec), _lib.ptr(out))
+        tail = (float(self.momentum), int(bool(self.nesterov)), int(accumulate))
+        if g.dtype in _lib.HALF:
+            _lib.check(L.dgc_compensate16_clip(*head, _lib.ptr(vec32) if accumulate else None, mmt.numel(), *tail,
+                                               _lib.VD[g.dtype], *_lib.clip_args(clip), _lib.stream_of(g.device)),
+                       "dgc_compensate16_clip")
+        else:   # no samples: (samples, start, stride, count) = (NULL, 0, 1, 0)
+            _lib.check(L.dgc_compensate_clip(*head, mmt.numel(), *tail, None, 0, 1, 0, *_lib.clip_args(clip),
+                                             _lib.stream_of(g.device)), "dgc_compensate_clip")
         return vec if accumulate else out
 
     def update(self, name, ctx):

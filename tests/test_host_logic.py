@@ -59,6 +59,38 @@ def test_int32_default_off_and_dtypes():
     assert (p.vdtype, p.idtype) == (1, 1)
 
 
+def test_select_params_builder():
+    """_lib.select_params is the one place a dgc_select_params is filled: with a compressor's
+    settings it equals the compressor's own record field for field; _lib.clip_args turns
+    fused_clip's triple (or None) into a *_clip entry point's three arguments."""
+    from dgc import _lib
+    comp = quiet(DGCCompressor, 0.001, fp16_values=True, int32_indices=True)
+    quiet(comp.initialize, [("w", (5000, [5000]))])
+    numel, _, k, S, _, _ = comp.attributes["w"]
+    assert numel == 5000
+    for masking, update, dt in ((True, True, torch.float32), (False, False, torch.bfloat16)):
+        p = comp._select_params("w", masking, update, dt)
+        q = _lib.select_params(numel, k, S, comp.compress_upper_bound, comp.compress_lower_bound,
+                               comp.max_adaptation_iters, comp.resample, masking, update, torch.float16, torch.int32,
+                               thr_dtype=dt)
+        for field, _ in _lib.SelectParams._fields_:
+            assert getattr(p, field) == getattr(q, field), field
+        assert (p.vdtype, p.idtype, p.thr_dtype) == (1, 1, _lib.VD[dt])
+        assert (p.masking, p.update_memory, p.resample_order, p.status_sink) == (int(masking), int(update), 0, None)
+        assert (p.upper_count, p.lower_count) == (math.floor(k * 1.3), math.ceil(0.8 * k))
+    assert comp._select_params("w", True, True) is comp._select_params("w", True, True)   # cached
+    s = _lib.select_params(10, 2, 10, 1.3, 0.8, 10, True, True, 2, torch.float32, torch.int64,
+                           resample_order="index", status_sink=4096)
+    assert (s.update_memory, s.resample_order, s.status_sink, s.thr_dtype) == (2, 1, 4096, 0)
+
+    assert _lib.NO_CLIP == (0, None, 0.0)
+    assert _lib.clip_args(None) == _lib.NO_CLIP
+    coef = torch.ones(1)
+    kind, ptr, value = _lib.clip_args((1, coef, 0.25))
+    assert (kind, ptr.value, value) == (1, coef.data_ptr(), 0.25)
+    assert _lib.clip_args((2, None, 3.0)) == (2, None, 3.0)
+
+
 def test_product_path_refuses_cpu_tensors():
     mem = DGCSGDMemory(momentum=0.9)
     comp = quiet(DGCCompressor, 0.01, memory=mem)
