@@ -253,3 +253,192 @@ extern "C" int dgc_sgd_step(float* const* params, const float* const* grads, flo
     }
     return DGC_OK;
 }
+
+// ---------------------------------------------------------------- sparse step
+// dgc_apply_packed: DGCSGD.step on the flat bucket without a dense gradient. `acc` holds
+// the decompressed gradient (dgc_scatter_packed of the gathered payload onto +0.0): +0.0
+// everywhere but at <= W * k gathered indices. The kernels walk the payload's entries
+// (all W runs) instead of the N elements; an entry takes its slot with a 32-bit atomic
+// exchange against +0.0 (relaxed, agent scope: an integer swap, never a float add), so
+// exactly one entry per distinct index gets the sum — whichever wins computes the same
+// result — duplicates across ranks get +0.0, and acc is +0.0 again when the walk ends.
+//
+// An entry whose slot holds +0.0 (all bits zero) is skipped, which is exact:
+//   wd == 0:  the reference computes fma(+0, -lr, p) = p + (-0) = p for every p, +-0
+//             included (lr >= 0, so -lr carries the sign bit even at lr = 0);
+//   wd != 0:  the dense pass below already computed the g = +0 result.
+// -0.0 and NaN have nonzero bits and are applied.
+//
+//   wd == 0:  k_apply_entries<APPLY>: p[i] = fma(g, -lr, p[i]), O(W k) in all.
+//   wd != 0:  k_apply_entries<STASH>: stash[q] = p[i] (entry q = rank * capacity + slot;
+//               duplicates store the same value);
+//             k_sgd_zero_grad: K7 with g = +0.0 and no gradient load, 16 (8 without
+//               momentum) B per element against K7's 20 (12). The d + 0 add stays: with
+//               p = -0.0, wd * p = -0 and the reference's d.add(grad) makes it +0;
+//             k_apply_entries<FIXUP>: the winner recomputes its element from stash[q] and
+//               the new buf[i] (which does not depend on g) with g.
+// The walk reads the header counts as the scatter does (RunSrc::get_raw: clamped to
+// [0, capacity]), so it visits exactly the entries the scatter summed; an index outside
+// [0, n) is skipped before any access. The scatter flagged both.
+namespace dgc {
+
+int64_t payload_layout(int64_t capacity, int vd, int id, int64_t* voff, int64_t* ioff);   // decompress.hip
+
+enum { kApply = 0, kApplyStash = 1, kApplyFixup = 2 };
+
+struct ApplySrc {
+    const char* payload;
+    int64_t stride, ioff, capacity;
+};
+
+template <int ID, int MODE, bool MOM>
+__global__ void __launch_bounds__(kBlock)
+k_apply_entries(ApplySrc src, float* __restrict__ acc, float* __restrict__ p, const float* __restrict__ buf,
+                float* __restrict__ stash, int64_t n, SgdHyper h) {
+    const int r = (int)blockIdx.y;
+    const char* base = src.payload + (int64_t)r * src.stride;
+    long long cnt = *reinterpret_cast<const long long*>(base);
+    cnt = cnt < 0 ? 0 : (cnt > src.capacity ? src.capacity : cnt);
+    for (long long e = (long long)blockIdx.x * kBlock + threadIdx.x; e < cnt; e += (long long)gridDim.x * kBlock) {
+        const long long i = ID == DGC_I32 ? (long long)reinterpret_cast<const int32_t*>(base + src.ioff)[e]
+                                          : (long long)reinterpret_cast<const int64_t*>(base + src.ioff)[e];
+        if (i < 0 || i >= n) continue;
+        const int64_t q = (int64_t)r * src.capacity + e;
+        if (MODE == kApplyStash) {
+            stash[q] = p[i];
+            continue;
+        }
+        const uint32_t gb = __hip_atomic_exchange(reinterpret_cast<uint32_t*>(acc + i), 0u, __ATOMIC_RELAXED,
+                                                  __HIP_MEMORY_SCOPE_AGENT);
+        if (gb == 0u) continue;   // +0.0: a duplicate's second visit, or a sum of +0.0 (see above)
+        const float g = __uint_as_float(gb);
+        if (MODE == kApply) {
+            p[i] = __fmaf_rn(g, h.neg_lr, p[i]);
+        } else {
+            const float p_old = stash[q];
+            float d = __fmul_rn(p_old, h.wd);
+            if (MOM) {
+                const float b = buf[i];
+                d = h.nesterov ? __fmaf_rn(b, h.mom, d) : b;
+            }
+            d = __fadd_rn(d, g);
+            p[i] = __fmaf_rn(d, h.neg_lr, p_old);
+        }
+    }
+}
+
+// K7 with weight decay on one tensor and g = +0.0: k_sgd's load and store shape without
+// the gradient stream.
+template <bool MOM>
+__global__ void __launch_bounds__(kBlock)
+k_sgd_zero_grad(float* __restrict__ p, float* __restrict__ buf, int64_t n, int32_t first_i, SgdHyper h) {
+    const bool first = first_i != 0;
+    const int64_t base = (int64_t)blockIdx.x * kSgdPerBlock;
+    const bool vec = aligned16(p) && (!MOM || aligned16(buf));
+    if (vec && base + kSgdPerBlock <= n) {
+        float4 pv[4], bv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t i = base + (int64_t)(u * kBlock + threadIdx.x) * 4;
+            pv[u] = ld_nt(reinterpret_cast<const float4*>(p + i));
+            if (MOM && !first) bv[u] = ld_nt(reinterpret_cast<const float4*>(buf + i));
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t i = base + (int64_t)(u * kBlock + threadIdx.x) * 4;
+            float4 o;
+            o.x = sgd1<true, MOM>(pv[u].x, 0.f, bv[u].x, first, h);
+            o.y = sgd1<true, MOM>(pv[u].y, 0.f, bv[u].y, first, h);
+            o.z = sgd1<true, MOM>(pv[u].z, 0.f, bv[u].z, first, h);
+            o.w = sgd1<true, MOM>(pv[u].w, 0.f, bv[u].w, first, h);
+            st_nt(reinterpret_cast<float4*>(p + i), o);
+            if (MOM) st_nt(reinterpret_cast<float4*>(buf + i), bv[u]);
+        }
+        return;
+    }
+    const int64_t end = base + kSgdPerBlock < n ? base + kSgdPerBlock : n;
+    for (int64_t i = base + threadIdx.x; i < end; i += kBlock) {
+        float b = MOM && !first ? buf[i] : 0.f;
+        p[i] = sgd1<true, MOM>(p[i], 0.f, b, first, h);
+        if (MOM) buf[i] = b;
+    }
+}
+
+static size_t apply_workspace(int32_t world, int64_t capacity) {
+    if (world < 1 || capacity < 0) return 0;
+    const int64_t slots = (int64_t)world * capacity;
+    return align_up((size_t)(slots > 0 ? slots : 1) * sizeof(float), 256);
+}
+
+template <int ID>
+static int apply_packed(const ApplySrc& src, int32_t world, float* acc, float* p, float* buf, int32_t first,
+                        int64_t n, const SgdHyper& h, bool mom, float* stash, hipStream_t s) {
+    const dim3 grid((unsigned)grid_for(src.capacity, kBlock, kMaxGrid / 2), (unsigned)world), block(kBlock);
+    const bool entries = src.capacity > 0;
+    if (h.wd == 0.f) {
+        if (entries) {
+            hipLaunchKernelGGL((k_apply_entries<ID, kApply, false>), grid, block, 0, s, src, acc, p, nullptr, nullptr, n,
+                               h);
+            DGC_LAUNCHED();
+        }
+        return DGC_OK;
+    }
+    if (entries) {
+        hipLaunchKernelGGL((k_apply_entries<ID, kApplyStash, false>), grid, block, 0, s, src, acc, p, nullptr, stash, n,
+                           h);
+        DGC_LAUNCHED();
+    }
+    const dim3 dense((unsigned)ceil_div(n, (int64_t)kSgdPerBlock));
+    if (mom)
+        hipLaunchKernelGGL(k_sgd_zero_grad<true>, dense, block, 0, s, p, buf, n, first, h);
+    else
+        hipLaunchKernelGGL(k_sgd_zero_grad<false>, dense, block, 0, s, p, nullptr, n, 0, h);
+    DGC_LAUNCHED();
+    if (entries) {
+        if (mom)
+            hipLaunchKernelGGL((k_apply_entries<ID, kApplyFixup, true>), grid, block, 0, s, src, acc, p, buf, stash, n,
+                               h);
+        else
+            hipLaunchKernelGGL((k_apply_entries<ID, kApplyFixup, false>), grid, block, 0, s, src, acc, p, nullptr, stash,
+                               n, h);
+        DGC_LAUNCHED();
+    }
+    return DGC_OK;
+}
+
+}  // namespace dgc
+
+extern "C" size_t dgc_apply_packed_workspace(int32_t world, int64_t capacity) {
+    return dgc::apply_workspace(world, capacity);
+}
+
+extern "C" int dgc_apply_packed(const void* payload, int32_t world, int64_t rank_stride, int64_t capacity,
+                                int32_t vdtype, int32_t idtype, float* acc, float* param, float* buf, int32_t first,
+                                int64_t n, float lr, float momentum, float dampening, float weight_decay,
+                                int32_t nesterov, void* ws, size_t ws_bytes, void* stream) {
+    using namespace dgc;
+    if (!payload || !acc || !param) DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed: null payload, acc or param");
+    if (world < 1 || world > 64) DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed: world %d outside 1..64", world);
+    if ((vdtype != DGC_F32 && vdtype != DGC_F16) || (idtype != DGC_I64 && idtype != DGC_I32))
+        DGC_FAIL(DGC_ERR_DTYPE, "dgc_apply_packed: unsupported value/index dtype (%d, %d)", vdtype, idtype);
+    if (capacity < 0 || n < 1) DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed: capacity < 0 or n < 1");
+    if (ceil_div(n, (int64_t)kSgdPerBlock) > 0x7FFFFFFFLL) DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed: n too large");
+    int64_t ioff = 0;
+    const int64_t min_stride = payload_layout(capacity, vdtype, idtype, nullptr, &ioff);
+    if (rank_stride < min_stride)
+        DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed: rank_stride %lld < layout %lld", (long long)rank_stride,
+                 (long long)min_stride);
+    // lr >= 0 (a NaN fails too): the skip of a +0.0 slot needs -lr to carry the sign bit
+    if (!(lr >= 0.f)) DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed: lr must be >= 0");
+    const bool wd = weight_decay != 0.f, mom = wd && momentum != 0.f;
+    if (mom && !buf) DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed: weight-decay momentum needs buf");
+    const size_t need = apply_workspace(world, capacity);
+    if (wd && (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 3)))
+        DGC_FAIL(DGC_ERR_WORKSPACE, "dgc_apply_packed: weight decay needs a workspace of %zu bytes, 4-B aligned", need);
+    const SgdHyper h{weight_decay, momentum, 1.f - dampening, -lr, nesterov};
+    const ApplySrc src{static_cast<const char*>(payload), rank_stride, ioff, capacity};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* stash = static_cast<float*>(ws);
+    if (idtype == DGC_I32) return apply_packed<DGC_I32>(src, world, acc, param, buf, first, n, h, mom, stash, s);
+    return apply_packed<DGC_I64>(src, world, acc, param, buf, first, n, h, mom, stash, s);
+}

@@ -291,6 +291,9 @@ _SIGNATURES = {
     "dgc_sgd_step16": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(_P),
                                       ctypes.POINTER(_I64), ctypes.POINTER(_I32), _I32, _F, _F, _F, _F, _I32, _I32,
                                       _P]),
+    "dgc_apply_packed_workspace": (_SZ, [_I32, _I64]),
+    "dgc_apply_packed": (ctypes.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _I32, _I64, _F, _F, _F, _F, _I32,
+                                        _P, _SZ, _P]),
 }
 
 _lib = None

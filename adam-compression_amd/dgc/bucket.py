@@ -41,6 +41,11 @@ one call per precision, ``dgc_compress_begin_clip`` / ``dgc_compress_begin16_cli
 them (``_lib.NO_CLIP`` without a clip) — stream-ordered, nothing read back; ``clip_coef``
 holds the device coefficient of the last step. The gradient stays as it was.
 
+``step_apply(grad, optimizer)`` (fp32, one exchange part) ends the step with the optimizer's
+update instead of a dense output: ``apply`` scatters the gathered entries into the bucket's
+own accumulator and ``dgc_apply_packed`` steps the parameter from them
+(``DGCSGD.step_sparse``), bit for bit ``step(grad, out)`` then ``DGCSGD.step()``.
+
 The numerics are those of the drop-in ``DGCCompressor`` + ``DGCSGDMemory`` (same
 kernels); the sample start is drawn from a ``random.Random`` seeded identically on
 every rank, one draw per step, like the reference's global ``random`` call.
@@ -291,6 +296,72 @@ class DGCBucket(ReceiveSide):
                     self._ev_go.record(torch.cuda.current_stream(self.device))
                 elif name == "allgather":  # ... and is enqueued behind the RCCL launch
                     self._zero_on_side(out, False)
+
+    # ---------------------------------------------------------------- sparse optimizer step
+    _acc = _apply_ws = None   # apply's accumulator (+0.0 between steps) and stash, made on first use
+
+    def _require_param(self, t, name):
+        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        if not (torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype == torch.float32
+                and t.is_contiguous() and t.numel() == self.numel):
+            got = f"{t.dtype} [{t.numel()}] on {t.device}" if torch.is_tensor(t) else type(t).__name__
+            raise ValueError(f"DGCBucket.apply: {name} must be a contiguous fp32 CUDA tensor of {self.numel} elements "
+                             f"on {dev} (got {got})")
+
+    def apply(self, param, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, momentum_buffer=None,
+              first=False):
+        """In place of ``decompress(out)`` after ``exchange()``: DGCSGD's step on ``param``
+        (dgc/optim/sgd.py:42-68) from the gathered entries, bit for bit ``decompress(p.grad)``
+        then ``DGCSGD.step()``, with no dense gradient written for the optimizer to read back.
+        The entries are scattered (K6, unchanged: rank-order sums, 1/W, status) into ``acc``,
+        the bucket's own accumulator, +0.0 between steps; ``dgc_apply_packed`` then walks them,
+        takes each sum out of ``acc`` and updates ``param`` — O(W * k) without weight decay, a
+        dense pass over ``param`` (and ``momentum_buffer``) that loads no gradient with it.
+        ``momentum_buffer`` / ``first``: DGCSGD's ``state[p]["momentum_buffer"]`` and whether
+        this step creates it (needed when weight_decay and momentum are both nonzero).
+        ``fill="sparse"``'s memory of the last ``out`` is left alone."""
+        if self.half:
+            raise NotImplementedError(f"DGCBucket.apply: fp32 parameters only (a {self.dtype} bucket takes decompress "
+                                      "and DGCSGD.step)")
+        if self.rx.parts > 1:
+            raise ValueError(f"DGCBucket.apply: the exchange is split in {self.rx.parts} parts, whose part-major "
+                             "gather layout apply does not walk; construct the bucket with exchange_parts=1")
+        self._require_param(param, "param")
+        use_buf = weight_decay != 0 and momentum != 0
+        if use_buf:
+            self._require_param(momentum_buffer, "momentum_buffer")
+        if not lr >= 0:
+            raise ValueError(f"DGCBucket.apply: lr must be >= 0 (got {lr})")
+        L, rx = self._L, self.rx
+        if self._acc is None:
+            self._acc = torch.zeros(self.numel, dtype=torch.float32, device=param.device)
+            self._apply_ws = torch.empty(L.dgc_apply_packed_workspace(self.world, self.k), dtype=torch.uint8,
+                                         device=param.device)
+        cur = rx.gathered
+        # the exchange's scatter, not Receiver.scatter: acc is not a decompress output to remember
+        rx.xchg.scatter(cur, rx._take(), self._acc, rx.scale, False)
+        _lib.check(L.dgc_apply_packed(cur.data_ptr(), self.world, rx.rank_stride, self.k, _lib.VD[self.vdtype],
+                                      _lib.ID[self.idtype], self._acc.data_ptr(), param.data_ptr(),
+                                      momentum_buffer.data_ptr() if use_buf else None, int(bool(first)), self.numel,
+                                      float(lr), float(momentum), float(dampening), float(weight_decay),
+                                      int(bool(nesterov)), self._apply_ws.data_ptr(), self._apply_ws.numel(),
+                                      _lib.stream_of(self.device)), "dgc_apply_packed")
+
+    def step_apply(self, grad, optimizer, param=None, events=None):
+        """compensate -> threshold -> select -> allgather -> ``optimizer.step_sparse(self,
+        param)`` (a ``dgc.optim.DGCSGD``): ``step(grad, out)`` followed by the optimizer's
+        ``step()`` on ``p.grad = out``, without ``out``. ``events`` as in ``step``; the last
+        phase is ``"apply"``."""
+        ev = events or {}
+        self.status.check()   # before anything of this step is issued
+        for name, fn in (("compensate", lambda: self.compensate(grad)), ("select", self.select),
+                         ("allgather", self.exchange), ("apply", lambda: optimizer.step_sparse(self, param))):
+            pair = ev.get(name)
+            if pair:
+                pair[0].record()
+            fn()
+            if pair:
+                pair[1].record()
 
     def last_info(self):
         self.status.check(sync=True)

@@ -115,6 +115,37 @@ class DGCSGD(Optimizer):
             _lib.check(L.dgc_sgd_step16(*args, _lib.VD[dt], _lib.stream_of(dev)), "dgc_sgd_step16")
 
     @torch.no_grad()
+    def step_sparse(self, bucket, param=None):
+        """``step()`` of one fp32 parameter whose gradient is the flat ``bucket``'s exchanged
+        step (``dgc.bucket.DGCBucket``, after its ``exchange()``): the update is applied from
+        the gathered entries (``DGCBucket.apply`` -> ``dgc_apply_packed``), bit for bit what
+        ``bucket.decompress(p.grad); step()`` leaves in ``p`` and ``state[p]``. ``p.grad`` is
+        never read. ``param``: the optimizer's only parameter when omitted."""
+        if param is None:
+            params = [p for group in self.param_groups for p in group["params"]]
+            if len(params) != 1:
+                raise ValueError(f"DGCSGD.step_sparse: name the parameter (the optimizer holds {len(params)})")
+            param = params[0]
+        group = next((g for g in self.param_groups if any(q is param for q in g["params"])), None)
+        if group is None:
+            raise ValueError("DGCSGD.step_sparse: param is not one of the optimizer's parameters")
+        wd, mom = float(group["weight_decay"]), float(group["momentum"])
+        state = self.state[param]
+        buf, first = None, False
+        if wd != 0 and mom != 0:   # the momentum buffer as _fused_group creates it
+            buf = state.get("momentum_buffer")
+            first = buf is None
+            if first:
+                buf = state["momentum_buffer"] = torch.empty_like(param.data)
+        try:
+            bucket.apply(param.data, float(group["lr"]), mom, float(group["dampening"]), wd, bool(group["nesterov"]),
+                         momentum_buffer=buf, first=first)
+        except Exception:
+            if first:   # refused before anything ran: no uninitialised buffer stays behind
+                del state["momentum_buffer"]
+            raise
+
+    @torch.no_grad()
     def step(self, closure=None):
         loss = None
         if closure is not None:

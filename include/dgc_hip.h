@@ -24,6 +24,8 @@
  *                         previous call's result (zero_() as a sparse re-zero);
  *                         dgc_clear_packed + dgc_scatter_packed_cleared: its two halves
  *   dgc_sgd_step          DGCSGD.step (weight-decay momentum + update) dgc/optim/sgd.py:42-68
+ *   dgc_apply_packed      the same step of one parameter from the gathered payload's entries
+ *                         (the decompressed gradient never read as a dense tensor)
  *   dgc_compensate16, dgc_mask_indices16, dgc_widen16, dgc_decompress16
  *                         the same memory / decompress for bf16 / fp16 parameters
  *                         (dgc/memory.py:43-77, dgc/compression.py:179-194 on a
@@ -501,6 +503,25 @@ int dgc_compensate_ranks(const void* src, int32_t src_dtype, int32_t world, int6
 int dgc_sgd_step(float* const* params, const float* const* grads, float* const* bufs, const int64_t* numels,
                  const int32_t* first, int32_t count, float lr, float momentum, float dampening,
                  float weight_decay, int32_t nesterov, void* stream);
+/* K7 sparse: DGCSGD.step of ONE fp32 parameter straight from the gathered packed payload
+ * (dgc_payload_layout; vdtype / idtype only select the layout and the index width), with no
+ * dense gradient read: O(world * capacity) work when weight_decay == 0; with weight decay a
+ * dense pass over param (+ buf) that loads no gradient, between two O(world * capacity)
+ * passes over the entries.
+ * Precondition: acc[0..n) holds exactly dgc_scatter_packed's result of this `payload`
+ * (same world / rank_stride / capacity / dtypes / n and the 1/W scale) onto +0.0, and
+ * lr >= 0. Postcondition: acc is +0.0 everywhere again; param (and buf) are bit for bit
+ * what dgc_sgd_step would have left with acc as the gradient. buf / first as in
+ * dgc_sgd_step (buf is read only when weight_decay != 0 and momentum != 0). ws:
+ * dgc_apply_packed_workspace bytes (4 B per gathered slot, rounded up to 256), needed
+ * when weight_decay != 0, else it may be NULL. A header count outside [0, capacity] is
+ * clamped as the scatter clamps it and an index outside [0, n) is skipped; the scatter
+ * has reported both (dgc_decompress_status, the bound sink). Stream-ordered. */
+size_t dgc_apply_packed_workspace(int32_t world, int64_t capacity);
+int dgc_apply_packed(const void* payload, int32_t world, int64_t rank_stride, int64_t capacity, int32_t vdtype,
+                     int32_t idtype, float* acc, float* param, float* buf, int32_t first, int64_t n, float lr,
+                     float momentum, float dampening, float weight_decay, int32_t nesterov, void* ws, size_t ws_bytes,
+                     void* stream);
 /* K7-16: the same for bf16 / fp16 parameters (dtype DGC_BF16 / DGC_F16; params, grads,
  * bufs 16-bit arrays of that dtype): every op rounds to the dtype as the reference's
  * torch-CPU ops on a 16-bit tensor do — alpha rounded to the dtype; `add(alpha)` rounds
