@@ -19,6 +19,12 @@
 // HBM: read p, g (+ buf), write p (+ buf): 12 or 20 B per element. One launch covers
 // up to kSgdMaxTensors tensors (a block table in the kernel arguments, like a
 // multi-tensor apply); each block streams 16-B vectors of one tensor.
+//
+// The entry points check the WHOLE table before the first chunk is launched: a refusal
+// leaves every tensor untouched. An entry with numels[i] == 0 may carry null pointers (a
+// zero-element device tensor has a null data pointer): it gets no block, so none of its
+// pointers is read, and the step is the no-op the reference's is. With n > 0 a null
+// params[i] / grads[i] (or bufs[i], when a momentum buffer is in use) is refused.
 #include "dgc_common.hpp"
 
 namespace dgc {
@@ -40,6 +46,22 @@ struct SgdHyper {
     float wd, mom, damp_alpha, neg_lr;
     int32_t nesterov;
 };
+
+// The table of dgc_sgd_step / dgc_sgd_step16, every entry, before anything is launched.
+static int sgd_check_table(const char* who, const void* const* params, const void* const* grads,
+                           const void* const* bufs, const int64_t* numels, int32_t count, bool mom,
+                           int64_t per_block) {
+    int64_t blocks = 0;   // of the chunk (one launch) tensor i is in
+    for (int32_t i = 0; i < count; ++i) {
+        if (numels[i] < 0) DGC_FAIL(DGC_ERR_INVALID, "%s: tensor %d: n < 0", who, i);
+        if (numels[i] > 0 && (!params[i] || !grads[i] || (mom && !bufs[i])))
+            DGC_FAIL(DGC_ERR_INVALID, "%s: tensor %d: null pointer", who, i);
+        if (i % kSgdMaxTensors == 0) blocks = 0;
+        blocks += ceil_div(numels[i], per_block);
+        if (blocks > 0x7FFFFFFF) DGC_FAIL(DGC_ERR_INVALID, "%s: too many elements in one group", who);
+    }
+    return DGC_OK;
+}
 
 template <bool WD, bool MOM>
 __device__ __forceinline__ float sgd1(float p, float g, float& b, bool first, const SgdHyper& h) {
@@ -176,7 +198,8 @@ extern "C" int dgc_sgd_step16(void* const* params, const void* const* grads, voi
         DGC_FAIL(DGC_ERR_INVALID, "dgc_sgd_step16: null tensor table");
     if (dtype != DGC_BF16 && dtype != DGC_F16) DGC_FAIL(DGC_ERR_DTYPE, "dgc_sgd_step16: dtype must be bf16 or fp16");
     const bool wd = weight_decay != 0.f, mom = wd && momentum != 0.f;
-    if (mom && (!bufs || !first)) DGC_FAIL(DGC_ERR_INVALID, "dgc_sgd_step16: momentum needs buffers");
+    if (count > 0 && mom && (!bufs || !first)) DGC_FAIL(DGC_ERR_INVALID, "dgc_sgd_step16: momentum needs buffers");
+    DGC_TRY(sgd_check_table("dgc_sgd_step16", params, grads, bufs, numels, count, mom, kSgd16PerBlock));
     SgdHyper h{weight_decay, momentum, 1.f - dampening, -lr, nesterov};
     hipStream_t s = static_cast<hipStream_t>(stream);
     for (int32_t c0 = 0; c0 < count; c0 += kSgdMaxTensors) {
@@ -184,8 +207,6 @@ extern "C" int dgc_sgd_step16(void* const* params, const void* const* grads, voi
         int64_t blocks = 0;
         for (int32_t j = 0; j < kSgdMaxTensors && c0 + j < count; ++j) {
             const int32_t i = c0 + j;
-            if (!params[i] || !grads[i] || numels[i] < 0 || (mom && !bufs[i]))
-                DGC_FAIL(DGC_ERR_INVALID, "dgc_sgd_step16: tensor %d: null pointer or n < 0", i);
             t.p[t.count] = static_cast<uint16_t*>(params[i]);
             t.g[t.count] = static_cast<const uint16_t*>(grads[i]);
             t.buf[t.count] = mom ? static_cast<uint16_t*>(bufs[i]) : nullptr;
@@ -193,7 +214,6 @@ extern "C" int dgc_sgd_step16(void* const* params, const void* const* grads, voi
             t.first[t.count] = mom ? first[i] : 0;
             t.block0[t.count] = (int32_t)blocks;
             blocks += ceil_div(numels[i], (int64_t)kSgd16PerBlock);
-            if (blocks > 0x7FFFFFFF) DGC_FAIL(DGC_ERR_INVALID, "dgc_sgd_step16: too many elements in one group");
             t.count++;
         }
         t.block0[t.count] = (int32_t)blocks;
@@ -221,7 +241,10 @@ extern "C" int dgc_sgd_step(float* const* params, const float* const* grads, flo
     if (count < 0 || (count > 0 && (!params || !grads || !numels)))
         DGC_FAIL(DGC_ERR_INVALID, "dgc_sgd_step: null tensor table");
     const bool wd = weight_decay != 0.f, mom = wd && momentum != 0.f;
-    if (mom && (!bufs || !first)) DGC_FAIL(DGC_ERR_INVALID, "dgc_sgd_step: momentum needs buffers");
+    if (count > 0 && mom && (!bufs || !first)) DGC_FAIL(DGC_ERR_INVALID, "dgc_sgd_step: momentum needs buffers");
+    DGC_TRY(sgd_check_table("dgc_sgd_step", reinterpret_cast<const void* const*>(params),
+                            reinterpret_cast<const void* const*>(grads),
+                            reinterpret_cast<const void* const*>(bufs), numels, count, mom, kSgdPerBlock));
     SgdHyper h{weight_decay, momentum, 1.f - dampening, -lr, nesterov};
     hipStream_t s = static_cast<hipStream_t>(stream);
     for (int32_t c0 = 0; c0 < count; c0 += kSgdMaxTensors) {
@@ -229,8 +252,6 @@ extern "C" int dgc_sgd_step(float* const* params, const float* const* grads, flo
         int64_t blocks = 0;
         for (int32_t j = 0; j < kSgdMaxTensors && c0 + j < count; ++j) {
             const int32_t i = c0 + j;
-            if (!params[i] || !grads[i] || numels[i] < 0 || (mom && !bufs[i]))
-                DGC_FAIL(DGC_ERR_INVALID, "dgc_sgd_step: tensor %d: null pointer or n < 0", i);
             t.p[t.count] = params[i];
             t.g[t.count] = grads[i];
             t.buf[t.count] = mom ? bufs[i] : nullptr;
@@ -238,7 +259,6 @@ extern "C" int dgc_sgd_step(float* const* params, const float* const* grads, flo
             t.first[t.count] = mom ? first[i] : 0;
             t.block0[t.count] = (int32_t)blocks;
             blocks += ceil_div(numels[i], (int64_t)kSgdPerBlock);
-            if (blocks > 0x7FFFFFFF) DGC_FAIL(DGC_ERR_INVALID, "dgc_sgd_step: too many elements in one group");
             t.count++;
         }
         t.block0[t.count] = (int32_t)blocks;

@@ -12,7 +12,12 @@ K7 in ``csrc/sgd.hip``, for fp32; ``dgc_sgd_step16`` for bf16 / fp16): read p, g
 (fp32: ``add(alpha)`` is one fused multiply-add; 16-bit: every op rounds to the
 dtype, alpha too, with the CPU kernels' vector body / scalar tail — oracle
 ``dgcsgd_step16``, pinned to tests/golden/sgd16.*), so the weights are bit-identical to
-the reference's. For 16-bit parameters "the reference's" means what the fixtures pin: a
+the reference's. fp32 K7 is pinned to the oracle's ``dgcsgd_step32`` (an exact fused
+multiply-add in numpy), itself pinned to the reference's own CPU run by
+tests/golden/sgd32.*. A zero-element parameter is part of the fused launch like any
+other: its ``data_ptr()`` is 0, and the entry points accept a null pointer where
+``numels[i] == 0`` (no block, nothing read) — the no-op the reference's step is for it,
+with the same (empty) momentum buffer in the state. For 16-bit parameters "the reference's" means what the fixtures pin: a
 ONE-thread CPU run on the AVX2 kernels (32-element vector body; tests/golden/
 make_goldens.py sets torch.set_num_threads(1)). A multi-threaded CPU run gives every
 parallel chunk of a tensor over 32768 elements its own scalar tail, the AVX512 kernels

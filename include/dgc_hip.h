@@ -499,7 +499,12 @@ int dgc_compensate_ranks(const void* src, int32_t src_dtype, int32_t world, int6
  * params[i], grads[i] (and bufs[i], the momentum_buffer, when weight_decay != 0 and
  * momentum != 0) are fp32 device arrays of numels[i] elements; first[i] = 1 when the
  * buffer is created on this step (buf = wd * p). Rounding follows the reference's
- * torch-CPU ops (add with alpha is one fused multiply-add). Stream-ordered. */
+ * torch-CPU ops (add with alpha is one fused multiply-add). Stream-ordered.
+ * The whole table is checked before anything is launched (a refusal leaves every tensor
+ * untouched): count < 0, a null table, numels[i] < 0, or a null params[i] / grads[i] /
+ * needed bufs[i] with numels[i] > 0 is DGC_ERR_INVALID. An entry with numels[i] == 0 is a
+ * no-op and may carry null pointers (a zero-element device tensor's data pointer is null).
+ * dgc_sgd_step16 follows the same rules. */
 int dgc_sgd_step(float* const* params, const float* const* grads, float* const* bufs, const int64_t* numels,
                  const int32_t* first, int32_t count, float lr, float momentum, float dampening,
                  float weight_decay, int32_t nesterov, void* stream);

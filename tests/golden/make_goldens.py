@@ -712,8 +712,64 @@ def gen_sgd16(O):
         json.dump(meta, f, indent=1)
 
 
+# DGCSGD.step on fp32 parameters (dgc/optim/sgd.py:42-68; CPU, one thread): (label, lr,
+# momentum, dampening, weight_decay, nesterov). The last case, -lr = -0.0, shows what the
+# final add does to a -0.0 weight. At most 6 000 elements per case.
+SGD32_CASES = [
+    ("nest_wd", 0.1, 0.9, 0.0, 1e-4, True),
+    ("plain_wd_damp", 0.05, 0.9, 0.1, 5e-4, False),
+    ("wd_nomom", 0.1, 0.0, 0.0, 1e-4, False),
+    ("nowd", 0.1, 0.9, 0.0, 0.0, False),
+    ("heavy_damp", 0.3, 0.5, 0.25, 0.01, False),
+    ("lr0_nest", 0.0, 0.9, 0.0, 1e-4, True),
+]
+SGD32_SHAPES = [("a", (37,)), ("b", (64, 3, 3, 3)), ("c", (1000,)), ("d", (333, 7)), ("e", (16,))]
+
+
+def sgd32_inputs(gen, steps=3):
+    """The seeded inputs of an SGD32 case (the test regenerates them the same way): the
+    initial parameters, then each step's gradients, drawn in this order. The first
+    elements of "a" hold +0.0 and -0.0 weights (with -0.0 and ordinary gradients) and a
+    denormal weight and gradient."""
+    init = [torch.randn(s, generator=gen) * 0.5 for _, s in SGD32_SHAPES]
+    grads = [[torch.randn(s, generator=gen) * 0.01 for _, s in SGD32_SHAPES] for _ in range(steps)]
+    init[0][:5] = torch.tensor([0.0, -0.0, 0.0, -0.0, 1e-45])
+    for gs in grads:
+        gs[0][:2] = -0.0
+        gs[0][4] = 1e-44
+    return init, grads
+
+
+def gen_sgd32(O):
+    """Per case: the parameters after each of 3 DGCSGD steps on fp32 parameters, and the
+    momentum buffers after the last (32-bit patterns), from the seeded inputs of
+    ``sgd32_inputs`` (torch.Generator(5000 + case) normal draws; the test regenerates them)."""
+    torch.set_num_threads(1)
+    arrays, meta = {}, {}
+    bits = lambda t: t.detach().contiguous().view(torch.int32).numpy().copy()   # noqa: E731
+    for ci, (label, lr, mom, damp, wd, nest) in enumerate(SGD32_CASES):
+        init, grads = sgd32_inputs(torch.Generator().manual_seed(5000 + ci))
+        params = [torch.nn.Parameter(t) for t in init]
+        opt = O.DGCSGD(params, lr=lr, momentum=mom, dampening=damp, weight_decay=wd, nesterov=nest)
+        for s in range(3):
+            for p, g in zip(params, grads[s]):
+                p.grad = g
+            opt.step()
+            for (n, _), p in zip(SGD32_SHAPES, params):
+                arrays[f"{label}/s{s}/p/{n}"] = bits(p)
+                buf = opt.state[p].get("momentum_buffer")
+                if buf is not None and s == 2:
+                    arrays[f"{label}/buf/{n}"] = bits(buf)
+        meta[label] = dict(lr=lr, momentum=mom, dampening=damp, weight_decay=wd, nesterov=nest, steps=3,
+                           shapes=SGD32_SHAPES)
+        print(f"sgd32 {label}")
+    np.savez_compressed(os.path.join(HERE, "sgd32.npz"), **arrays)
+    with open(os.path.join(HERE, "sgd32.json"), "w") as f:
+        json.dump(meta, f, indent=1)
+
+
 GENERATORS = ("attributes", "compress", "decompress", "optimizer", "optimizer_resnet20", "optimizer_trace", "half",
-              "optimizer_multi", "sgd16")
+              "optimizer_multi", "sgd16", "sgd32")
 
 
 def main(which=GENERATORS):
@@ -737,6 +793,8 @@ def main(which=GENERATORS):
         gen_optimizer_multi(C, M, H, O)
     if "sgd16" in which:
         gen_sgd16(O)
+    if "sgd32" in which:
+        gen_sgd32(O)
 
 
 if __name__ == "__main__":

@@ -3,7 +3,8 @@
 Single process, C ABI: W hand-made rank payloads (as tests/test_gpu_split.py builds them) are
 scattered into a +0.0 accumulator with dgc_scatter_packed, then applied. ``param`` and the
 momentum buffer must be, bit for bit (compared as uint32), the reference's op sequence
-(dgc/optim/sgd.py:42-68) run with torch on the CPU over the oracle's decompress — and what
+(dgc/optim/sgd.py:42-68) run with torch on the CPU over the oracle's decompress — which must
+itself equal oracle.dgcsgd_step32, the expectation K7 is pinned to — and what
 the existing path (dgc_decompress_packed + dgc_sgd_step) leaves; the accumulator must be
 +0.0 everywhere after every call."""
 import ctypes
@@ -229,7 +230,13 @@ def run_case(L, N, W, cap, fp16, int32, hyper, make_runs, offset=False, garbage=
         good = [(wv[(i >= 0) & (i < N)], i[(i >= 0) & (i < N)]) for wv, (_, i) in zip(_wire(runs, fp16), runs)]
         assert bad_index or sum(len(i) for _, i in good) == idx_all.size
         g_ref = torch.from_numpy(O.decompress([v for v, _ in good], [i for _, i in good], N, W))
+        p_in, buf_in = p_ref.numpy().copy(), None if buf_ref is None else buf_ref.numpy().copy()
         buf_ref = ref_step(p_ref, buf_ref, g_ref, wd, mom, damp, nesterov)
+        # the second expectation: the fp32 oracle (pinned to the reference by tests/golden/sgd32.*)
+        p_o, buf_o = O.dgcsgd_step32(p_in, g_ref.numpy(), buf_in, LR, mom, damp, wd, nesterov)
+        assert np.array_equal(bits(p_o), bits(p_ref)), (hyper, step, "oracle / torch-CPU sequence")
+        if use_buf:
+            assert np.array_equal(bits(buf_o), bits(buf_ref)), (hyper, step, "oracle / torch-CPU sequence buffer")
         g = ap.gather(runs, garbage)
         first = use_buf and step == 0
         status = ap.apply(g, p_new, buf_new, first, wd, mom, damp, nesterov)
