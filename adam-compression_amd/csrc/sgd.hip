@@ -311,6 +311,15 @@ struct ApplySrc {
     int64_t stride, ioff, capacity;
 };
 
+// The fix-up of one gathered element of a weight-decay group: the element recomputed from its
+// stashed old value and the new buf (which does not depend on g) with its gradient g.
+__device__ __forceinline__ float sgd_fixup(float p_old, float g, float b, bool mom, const SgdHyper& h) {
+    float d = __fmul_rn(p_old, h.wd);
+    if (mom) d = h.nesterov ? __fmaf_rn(b, h.mom, d) : b;
+    d = __fadd_rn(d, g);
+    return __fmaf_rn(d, h.neg_lr, p_old);
+}
+
 template <int ID, int MODE, bool MOM>
 __global__ void __launch_bounds__(kBlock)
 k_apply_entries(ApplySrc src, float* __restrict__ acc, float* __restrict__ p, const float* __restrict__ buf,
@@ -335,14 +344,7 @@ k_apply_entries(ApplySrc src, float* __restrict__ acc, float* __restrict__ p, co
         if (MODE == kApply) {
             p[i] = __fmaf_rn(g, h.neg_lr, p[i]);
         } else {
-            const float p_old = stash[q];
-            float d = __fmul_rn(p_old, h.wd);
-            if (MOM) {
-                const float b = buf[i];
-                d = h.nesterov ? __fmaf_rn(b, h.mom, d) : b;
-            }
-            d = __fadd_rn(d, g);
-            p[i] = __fmaf_rn(d, h.neg_lr, p_old);
+            p[i] = sgd_fixup(stash[q], g, MOM ? buf[i] : 0.f, MOM, h);
         }
     }
 }
@@ -350,10 +352,9 @@ k_apply_entries(ApplySrc src, float* __restrict__ acc, float* __restrict__ p, co
 // K7 with weight decay on one tensor and g = +0.0: k_sgd's load and store shape without
 // the gradient stream.
 template <bool MOM>
-__global__ void __launch_bounds__(kBlock)
-k_sgd_zero_grad(float* __restrict__ p, float* __restrict__ buf, int64_t n, int32_t first_i, SgdHyper h) {
-    const bool first = first_i != 0;
-    const int64_t base = (int64_t)blockIdx.x * kSgdPerBlock;
+__device__ __forceinline__ void sgd_zero_grad_block(float* __restrict__ p, float* __restrict__ buf, int64_t n,
+                                                    bool first, const SgdHyper& h, int64_t block) {
+    const int64_t base = block * kSgdPerBlock;
     const bool vec = aligned16(p) && (!MOM || aligned16(buf));
     if (vec && base + kSgdPerBlock <= n) {
         float4 pv[4], bv[4];
@@ -382,6 +383,12 @@ k_sgd_zero_grad(float* __restrict__ p, float* __restrict__ buf, int64_t n, int32
         p[i] = sgd1<true, MOM>(p[i], 0.f, b, first, h);
         if (MOM) buf[i] = b;
     }
+}
+
+template <bool MOM>
+__global__ void __launch_bounds__(kBlock)
+k_sgd_zero_grad(float* __restrict__ p, float* __restrict__ buf, int64_t n, int32_t first_i, SgdHyper h) {
+    sgd_zero_grad_block<MOM>(p, buf, n, first_i != 0, h, (int64_t)blockIdx.x);
 }
 
 static size_t apply_workspace(int32_t world, int64_t capacity) {
@@ -461,4 +468,181 @@ extern "C" int dgc_apply_packed(const void* payload, int32_t world, int64_t rank
     float* stash = static_cast<float*>(ws);
     if (idtype == DGC_I32) return apply_packed<DGC_I32>(src, world, acc, param, buf, first, n, h, mom, stash, s);
     return apply_packed<DGC_I64>(src, world, acc, param, buf, first, n, h, mom, stash, s);
+}
+
+// ---------------------------------------------------------------- sparse step, multi-tensor
+// dgc_apply_packed_multi: the same step for the T tensors of a batch, side by side in one
+// flat index space, each with its parameter group's hyper-parameters (<= kApplyMaxGroups
+// sets in the kernel arguments). The rows (dgc_apply_row) live in device memory the caller
+// keeps: an entry finds its row by binary search over the offsets, a block of the dense
+// pass by binary search over block0. Three launches at most, whatever T is:
+//   k_apply_entries_multi<kApplyStash>  stash[q] = param[t][i - offset[t]] at the entries
+//                                       of weight-decay groups (skipped when there is none);
+//   k_sgd_zero_grad_multi               sgd_zero_grad_block over the tensors of weight-decay
+//                                       groups (those of the other groups own no block);
+//   k_apply_entries_multi<kApply>       every entry takes its slot of acc (a gap's is dropped);
+//                                       the winner applies fma(g, -lr, p) (wd == 0) or the
+//                                       fix-up from its stash (wd != 0).
+namespace dgc {
+
+constexpr int kApplyMaxGroups = 8;
+
+struct ApplyGroups {
+    SgdHyper h[kApplyMaxGroups];
+    int32_t count;
+};
+
+// groups.h[g] without a dynamically indexed copy of the kernel arguments
+__device__ __forceinline__ SgdHyper apply_group(const ApplyGroups& groups, int32_t g) {
+    SgdHyper h = groups.h[0];
+#pragma unroll
+    for (int j = 1; j < kApplyMaxGroups; ++j)
+        if (g == j) h = groups.h[j];
+    return h;
+}
+
+// The row holding flat index i: the last row with offset <= i, if i is inside it; else -1 (a
+// padding gap, or a row whose group is out of range).
+__device__ __forceinline__ int apply_row_of(const dgc_apply_row* __restrict__ rows, int32_t count, int64_t i,
+                                            int32_t groups) {
+    int lo = 0, hi = count;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (rows[mid].offset <= i) lo = mid;
+        else hi = mid;
+    }
+    const int64_t j = i - rows[lo].offset;
+    if (j < 0 || j >= rows[lo].numel || (uint32_t)rows[lo].group >= (uint32_t)groups) return -1;
+    return lo;
+}
+
+template <int ID, int MODE>
+__global__ void __launch_bounds__(kBlock)
+k_apply_entries_multi(ApplySrc src, float* __restrict__ acc, const dgc_apply_row* __restrict__ rows, int32_t count,
+                      float* __restrict__ stash, int64_t n, ApplyGroups groups) {
+    const int r = (int)blockIdx.y;
+    const char* base = src.payload + (int64_t)r * src.stride;
+    long long cnt = *reinterpret_cast<const long long*>(base);
+    cnt = cnt < 0 ? 0 : (cnt > src.capacity ? src.capacity : cnt);
+    for (long long e = (long long)blockIdx.x * kBlock + threadIdx.x; e < cnt; e += (long long)gridDim.x * kBlock) {
+        const long long i = ID == DGC_I32 ? (long long)reinterpret_cast<const int32_t*>(base + src.ioff)[e]
+                                          : (long long)reinterpret_cast<const int64_t*>(base + src.ioff)[e];
+        if (i < 0 || i >= n) continue;
+        const int t = apply_row_of(rows, count, i, groups.count);
+        const int64_t q = (int64_t)r * src.capacity + e;
+        if (MODE == kApplyStash) {
+            if (t < 0) continue;
+            if (apply_group(groups, rows[t].group).wd != 0.f) stash[q] = rows[t].param[i - rows[t].offset];
+            continue;
+        }
+        const uint32_t gb = __hip_atomic_exchange(reinterpret_cast<uint32_t*>(acc + i), 0u, __ATOMIC_RELAXED,
+                                                  __HIP_MEMORY_SCOPE_AGENT);
+        if (gb == 0u || t < 0) continue;   // +0.0 (as in k_apply_entries), or a gap's sum, dropped
+        const float g = __uint_as_float(gb);
+        const SgdHyper h = apply_group(groups, rows[t].group);
+        float* p = rows[t].param + (i - rows[t].offset);
+        if (h.wd == 0.f) {
+            *p = __fmaf_rn(g, h.neg_lr, *p);
+        } else {
+            const bool mom = h.mom != 0.f;
+            *p = sgd_fixup(stash[q], g, mom ? rows[t].momentum_buffer[i - rows[t].offset] : 0.f, mom, h);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_sgd_zero_grad_multi(const dgc_apply_row* __restrict__ rows, int32_t count, ApplyGroups groups) {
+    // the tensor of this block: the last row with block0 <= blockIdx.x (rows without blocks
+    // share their block0 with the row after them, so they are never the last)
+    const int64_t b = (int64_t)blockIdx.x;
+    int lo = 0, hi = count;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (rows[mid].block0 <= b) lo = mid;
+        else hi = mid;
+    }
+    const int64_t local = b - rows[lo].block0, n = rows[lo].numel;
+    if (local < 0 || local * kSgdPerBlock >= n || (uint32_t)rows[lo].group >= (uint32_t)groups.count) return;
+    const SgdHyper h = apply_group(groups, rows[lo].group);
+    if (h.wd == 0.f) return;
+    if (h.mom != 0.f)
+        sgd_zero_grad_block<true>(rows[lo].param, rows[lo].momentum_buffer, n, rows[lo].first != 0, h, local);
+    else
+        sgd_zero_grad_block<false>(rows[lo].param, nullptr, n, false, h, local);
+}
+
+template <int ID>
+static int apply_packed_multi(const ApplySrc& src, int32_t world, float* acc, int64_t n, const dgc_apply_row* rows,
+                              int32_t count, int64_t dense_blocks, const ApplyGroups& groups, bool any_wd,
+                              float* stash, hipStream_t s) {
+    const dim3 grid((unsigned)grid_for(src.capacity, kBlock, kMaxGrid / 2), (unsigned)world), block(kBlock);
+    const bool entries = src.capacity > 0;
+    if (any_wd) {
+        if (entries) {
+            hipLaunchKernelGGL((k_apply_entries_multi<ID, kApplyStash>), grid, block, 0, s, src, acc, rows, count,
+                               stash, n, groups);
+            DGC_LAUNCHED();
+        }
+        if (dense_blocks > 0) {
+            hipLaunchKernelGGL(k_sgd_zero_grad_multi, dim3((unsigned)dense_blocks), block, 0, s, rows, count, groups);
+            DGC_LAUNCHED();
+        }
+    }
+    if (entries) {
+        hipLaunchKernelGGL((k_apply_entries_multi<ID, kApply>), grid, block, 0, s, src, acc, rows, count, stash, n,
+                           groups);
+        DGC_LAUNCHED();
+    }
+    return DGC_OK;
+}
+
+}  // namespace dgc
+
+extern "C" size_t dgc_apply_packed_multi_workspace(int32_t world, int64_t capacity) {
+    return dgc::apply_workspace(world, capacity);
+}
+
+extern "C" int dgc_apply_packed_multi(const void* payload, int32_t world, int64_t rank_stride, int64_t capacity,
+                                      int32_t vdtype, int32_t idtype, float* acc, int64_t flat_numel,
+                                      const dgc_apply_row* table, int32_t count, int64_t dense_blocks,
+                                      const dgc_apply_hyper* hypers, int32_t groups, void* ws, size_t ws_bytes,
+                                      void* stream) {
+    using namespace dgc;
+    static_assert(sizeof(dgc_apply_row) == 48, "dgc_apply_row is mirrored by dgc/_lib.py");
+    if (!payload || !acc || !table || !hypers)
+        DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed_multi: null payload, acc, table or hypers");
+    if (world < 1 || world > 64) DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed_multi: world %d outside 1..64", world);
+    if ((vdtype != DGC_F32 && vdtype != DGC_F16) || (idtype != DGC_I64 && idtype != DGC_I32))
+        DGC_FAIL(DGC_ERR_DTYPE, "dgc_apply_packed_multi: unsupported value/index dtype (%d, %d)", vdtype, idtype);
+    if (capacity < 0 || count < 1 || flat_numel < 1)
+        DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed_multi: capacity < 0, count < 1 or flat_numel < 1");
+    if (groups < 1 || groups > kApplyMaxGroups)
+        DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed_multi: %d parameter groups outside 1..%d", groups, kApplyMaxGroups);
+    if (dense_blocks < 0 || dense_blocks > 0x7FFFFFFFLL)
+        DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed_multi: dense_blocks outside [0, 2^31)");
+    int64_t ioff = 0;
+    const int64_t min_stride = payload_layout(capacity, vdtype, idtype, nullptr, &ioff);
+    if (rank_stride < min_stride)
+        DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed_multi: rank_stride %lld < layout %lld", (long long)rank_stride,
+                 (long long)min_stride);
+    ApplyGroups gs{};
+    gs.count = groups;
+    bool any_wd = false;
+    for (int32_t g = 0; g < groups; ++g) {
+        // lr >= 0 (a NaN fails too): the skip of a +0.0 slot needs -lr to carry the sign bit
+        if (!(hypers[g].lr >= 0.f)) DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed_multi: group %d: lr must be >= 0", g);
+        gs.h[g] = SgdHyper{hypers[g].weight_decay, hypers[g].momentum, 1.f - hypers[g].dampening, -hypers[g].lr,
+                           hypers[g].nesterov};
+        any_wd = any_wd || hypers[g].weight_decay != 0.f;
+    }
+    const size_t need = apply_workspace(world, capacity);
+    if (any_wd && (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255)))
+        DGC_FAIL(DGC_ERR_WORKSPACE, "dgc_apply_packed_multi: weight decay needs a workspace of %zu bytes, 256-B aligned",
+                 need);
+    const ApplySrc src{static_cast<const char*>(payload), rank_stride, ioff, capacity};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* stash = static_cast<float*>(ws);
+    if (idtype == DGC_I32)
+        return apply_packed_multi<DGC_I32>(src, world, acc, flat_numel, table, count, dense_blocks, gs, any_wd, stash, s);
+    return apply_packed_multi<DGC_I64>(src, world, acc, flat_numel, table, count, dense_blocks, gs, any_wd, stash, s);
 }

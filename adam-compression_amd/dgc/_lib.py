@@ -188,6 +188,53 @@ class BatchDesc(ctypes.Structure):
                 ("deferred_masking", ctypes.c_int32), ("dtype", ctypes.c_int32),
                 ("resample_order", ctypes.c_int32), ("status_sink", ctypes.c_void_p)]
 
+class ApplyRow(ctypes.Structure):
+    """dgc_apply_row (include/dgc_hip.h): one tensor of dgc_apply_packed_multi's device table."""
+    _fields_ = [("param", ctypes.c_void_p), ("momentum_buffer", ctypes.c_void_p), ("offset", ctypes.c_int64),
+                ("numel", ctypes.c_int64), ("block0", ctypes.c_int64), ("first", ctypes.c_int32),
+                ("group", ctypes.c_int32)]
+
+
+class ApplyHyper(ctypes.Structure):
+    """dgc_apply_hyper: one parameter group's DGCSGD hyper-parameters."""
+    _fields_ = [("lr", ctypes.c_float), ("momentum", ctypes.c_float), ("dampening", ctypes.c_float),
+                ("weight_decay", ctypes.c_float), ("nesterov", ctypes.c_int32)]
+
+
+APPLY_BLOCK = 4096      # elements per block of the sparse step's dense pass (dgc_apply_row.block0)
+APPLY_MAX_GROUPS = 8    # hyper-parameter sets one dgc_apply_packed_multi call takes
+
+
+class ApplyTable:
+    """dgc_apply_packed_multi's tensor table: the rows on the host (what the last upload
+    held) and their copy in device memory. ``update(rows)`` takes the step's rows —
+    ``(param_ptr, buf_ptr, offset, numel, first, group, dense)`` per tensor, sorted by offset,
+    ``dense``: the tensor's group has weight decay — fills in ``block0`` and uploads only
+    when a row differs from what the device holds (a host comparison; no device traffic
+    otherwise)."""
+
+    def __init__(self, device):
+        self.device = device
+        self.key, self.dev, self.count, self.dense_blocks, self.uploads = None, None, 0, 0, 0
+
+    def update(self, rows):
+        key = tuple(rows)
+        if key == self.key:
+            return
+        arr, blocks = (ApplyRow * len(rows))(), 0
+        for r, (p, b, off, n, first, group, dense) in zip(arr, rows):
+            r.param, r.momentum_buffer, r.offset, r.numel = p, b, off, n
+            r.block0, r.first, r.group = blocks, int(first), group
+            if dense:
+                blocks += -(-n // APPLY_BLOCK)
+        host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+        if self.dev is None or self.dev.numel() != host.numel():
+            self.dev = torch.empty(host.numel(), dtype=torch.uint8, device=self.device)
+        self.dev.copy_(host)
+        self.key, self.count, self.dense_blocks = key, len(rows), blocks
+        self.uploads += 1
+
+
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
 _I32 = ctypes.c_int32
@@ -294,6 +341,9 @@ _SIGNATURES = {
     "dgc_apply_packed_workspace": (_SZ, [_I32, _I64]),
     "dgc_apply_packed": (ctypes.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _I32, _I64, _F, _F, _F, _F, _I32,
                                         _P, _SZ, _P]),
+    "dgc_apply_packed_multi_workspace": (_SZ, [_I32, _I64]),
+    "dgc_apply_packed_multi": (ctypes.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _I64, _P, _I32, _I64, _P, _I32, _P,
+                                              _SZ, _P]),
 }
 
 _lib = None

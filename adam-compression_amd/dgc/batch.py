@@ -109,6 +109,7 @@ class DGCBatch(ReceiveSide):
         # DGC_K5_BROKEN and the decompress's bad index / gathered count (a peer's payload
         # corrupted in transit), written by the kernels into pinned words, checked every step
         self.status = _lib.StatusSink("DGCBatch", dev)
+        self._acc = None   # apply()'s fp32 accumulator over the flat layout, made on first use
         self.set_ratio(compress_ratio)
 
     # ---------------------------------------------------------------- layout
@@ -145,6 +146,7 @@ class DGCBatch(ReceiveSide):
         _lib.check(L.dgc_batch_init(ctypes.byref(d), self.ws.data_ptr(), wsz, _lib.stream_of(self.device)),
                    "dgc_batch_init")
         self.capacity = sum(a[0] for a in self.attrs)
+        self._apply_ws = None   # apply()'s stash: a word per gathered slot of this capacity
         # a new layout: a new receive side (payload / gather buffers, exchange, decompress
         # workspace bound to ``status``), which remembers nothing of the previous step
         self.rx = Receiver(self.capacity, self.flat_numel, self.world, self.vdtype, self.idtype, self.device,
@@ -292,6 +294,44 @@ class DGCBatch(ReceiveSide):
         # (16-bit: zero_(), the runs in rank order, each add rounded, the 1/W scale: HalfExchange)
         self.rx.decompress(out, out.untyped_storage().data_ptr() == self.grad_flat.untyped_storage().data_ptr())
         return out
+
+    def apply(self, table, hypers):
+        """In place of ``decompress()`` after ``send()``: DGCSGD's step (dgc/optim/sgd.py:42-68)
+        on every tensor of the batch from the gathered entries, bit for bit ``decompress()``
+        then ``DGCSGD.step()`` on the output's views, with no dense gradient written or read.
+        ``table``: an ``_lib.ApplyTable`` whose rows are the batch's tensors in order (row t:
+        parameter and momentum buffer of ``names[t]``, ``offsets[t]``, ``numels[t]``);
+        ``hypers``: per parameter group of the table ``(lr, momentum, dampening, weight_decay,
+        nesterov)``. The entries are scattered (K6, unchanged: rank-order sums, 1/W, status)
+        into the batch's own accumulator, +0.0 between steps; ``dgc_apply_packed_multi`` then
+        walks them. ``fill="sparse"``'s memory of the last output is left alone."""
+        if self.half:
+            raise NotImplementedError(f"DGCBatch.apply: fp32 parameters only (a {self.dtype} batch takes decompress "
+                                      "and DGCSGD.step)")
+        rx = self.rx
+        if rx.parts > 1:
+            raise ValueError(f"DGCBatch.apply: the exchange is split in {rx.parts} parts, whose part-major gather "
+                             "layout apply does not walk; construct the batch with exchange_parts=1")
+        if table.count != len(self.names) or not 1 <= len(hypers) <= _lib.APPLY_MAX_GROUPS:
+            raise ValueError(f"DGCBatch.apply: a table of the batch's {len(self.names)} tensors and 1.."
+                             f"{_lib.APPLY_MAX_GROUPS} parameter groups (got {table.count} rows, {len(hypers)} groups)")
+        L = self._L
+        if self._acc is None:
+            self._acc = torch.zeros(self.flat_numel, dtype=torch.float32, device=self.device)
+        if self._apply_ws is None:
+            self._apply_ws = torch.empty(L.dgc_apply_packed_multi_workspace(self.world, self.capacity),
+                                         dtype=torch.uint8, device=self.device)
+        hs = (_lib.ApplyHyper * len(hypers))(*[_lib.ApplyHyper(float(lr), float(mom), float(damp), float(wd),
+                                                               int(bool(nesterov)))
+                                               for lr, mom, damp, wd, nesterov in hypers])
+        cur = rx.gathered
+        # the exchange's scatter, not Receiver.scatter: acc is not a decompress output to remember
+        rx.xchg.scatter(cur, rx._take(), self._acc, rx.scale, False)
+        _lib.check(L.dgc_apply_packed_multi(cur.data_ptr(), self.world, rx.rank_stride, self.capacity,
+                                            _lib.VD[self.vdtype], _lib.ID[self.idtype], self._acc.data_ptr(),
+                                            self.flat_numel, table.dev.data_ptr(), table.count, table.dense_blocks,
+                                            hs, len(hypers), self._apply_ws.data_ptr(), self._apply_ws.numel(),
+                                            _lib.stream_of(self.device)), "dgc_apply_packed_multi")
 
     def step(self, starts=None):
         self.compress(starts)

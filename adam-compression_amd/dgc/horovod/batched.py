@@ -117,9 +117,13 @@ def _draw():
 
 
 class BatchedStep:
-    def __init__(self, compression, named_parameters, fill="inline"):
+    def __init__(self, compression, named_parameters, fill="inline", apply=None):
         if fill not in ("inline", "sparse"):
             raise ValueError(f"batched DGC: fill must be 'inline' or 'sparse', not {fill!r}")
+        # batch="apply": the wrapped dgc.optim.DGCSGD, whose step on the compressed tensors is
+        # applied from the gathered entries (``_apply``); None: every step decompresses
+        self.opt = apply
+        self.apply_steps = self.dense_steps = 0   # steps of either kind (with a compressed tensor or not)
         self.comp = compression
         self.mem = compression.memory
         self.fill = fill
@@ -136,6 +140,12 @@ class BatchedStep:
         if self.mem.gradient_clipping is not None and (self.clip is None or self.half):
             raise NotImplementedError("DistributedOptimizer(batch=True): gradient clipping is fused for a local "
                                       "dgc.clip_grad function on fp32 parameters; anything else runs with batch=False")
+        if apply is not None:
+            if self.half:
+                raise NotImplementedError(f"DistributedOptimizer(batch='apply'): fp32 parameters only (got "
+                                          f"{self.dtype}); bf16 / fp16 parameters run with batch=True")
+            names = set(compression.attributes) if compression.compress_ratio < 1.0 else set()
+            self._apply_groups([p for n, p in self.named if n in names])   # more than 8 groups: refused here
         self.mem._before_read.append(self.flush)
         _lib.glue()   # the host glue must be there (fails loudly, like the library)
 
@@ -252,9 +262,12 @@ class BatchedStep:
                 moms[n] = mv
 
     # ------------------------------------------------------------------ step
-    def step(self, hook_order):
+    def step(self, hook_order, apply=False):
         """compress -> exchange -> decompress for every parameter; ``hook_order`` lists
-        the parameters in the order their hooks fired (the reference's compress order)."""
+        the parameters in the order their hooks fired (the reference's compress order).
+        ``apply`` (batch="apply", asked for by a ``step()`` that synchronizes itself and has no
+        closure): the compressed tensors are not decompressed but stepped from the gathered
+        entries and left without a ``.grad`` (``_apply``; a step it cannot take decompresses)."""
         glue = _glue()
         key = self._plan_key()
         if self._plan is None or self._plan["key"] != key:
@@ -263,6 +276,7 @@ class BatchedStep:
         plan = self._plan
         b = plan["batch"]
         dev = plan["dev"]
+        applied = False
         if b is not None:
             if plan["order"] != hook_order:
                 # the sample-start draw sequence of this hook order (backward's order is
@@ -316,9 +330,13 @@ class BatchedStep:
                 if own is not None:
                     dense_handle = comm.allgather_packed_async(own, out=plan["dense_gathered"])
         if b is not None:
-            b.send()   # the allgather (or its parts), waited for in b.decompress()
-            b.decompress()   # into the batch's output, then p.grad (dgc/compression.py:191-194)
-            glue.bind_grads(plan["comp_params"], plan["comp_views"])
+            b.send()   # the allgather (or its parts), waited for in b.decompress() / b.apply()
+            applied = apply and self._apply(plan)
+            if not applied:
+                b.decompress()   # into the batch's output, then p.grad (dgc/compression.py:191-194)
+                glue.bind_grads(plan["comp_params"], plan["comp_views"])
+        self.apply_steps += int(applied)
+        self.dense_steps += int(not applied)
         if plan["dense"]:
             mem = self.mem
             L = _lib.lib()
@@ -388,6 +406,78 @@ class BatchedStep:
         if wire is not dense_in:
             dense_in.copy_(wire)   # the fp16 round trip of a bf16 gradient
         return None
+
+    # ------------------------------------------------------------------ batch="apply"
+    def _apply_groups(self, comp_params):
+        """(the wrapped optimizer's parameter groups that hold a compressed parameter, each
+        compressed parameter's index into them); more than ``dgc_apply_packed_multi`` takes
+        hyper-parameter sets for is refused."""
+        owner = {id(p): gi for gi, g in enumerate(self.opt.param_groups) for p in g["params"]}
+        used = sorted({owner[id(p)] for p in comp_params})
+        if len(used) > _lib.APPLY_MAX_GROUPS:
+            raise ValueError(f"DistributedOptimizer(batch='apply'): {len(used)} parameter groups hold compressed "
+                             f"parameters; the sparse step takes {_lib.APPLY_MAX_GROUPS} (use batch=True)")
+        local = {gi: j for j, gi in enumerate(used)}
+        return [self.opt.param_groups[gi] for gi in used], [local[owner[id(p)]] for p in comp_params]
+
+    def _apply(self, plan):
+        """DGCSGD's step on the compressed tensors from the gathered entries
+        (``DGCBatch.apply`` -> ``dgc_apply_packed_multi``), in place of the decompress into
+        p.grad and K7's read of it: the weights and ``state[p]["momentum_buffer"]`` are what
+        ``decompress`` + ``DGCSGD.step()`` leave, bit for bit, and the tensors' ``.grad`` is
+        None afterwards (the wrapped ``step()`` that follows finds only the dense tensors'
+        gradients). Every group's hyper-parameters are read now. Returns False, having
+        touched nothing, when the step has to decompress: a split exchange, or a parameter or
+        existing momentum buffer that is not a contiguous fp32 tensor on the device.
+
+        The device table is the plan's: rebuilt with it, and uploaded again only when a row
+        differs from the last upload (``first`` after a buffer's first step, a parameter or
+        buffer at another address, a group's weight decay switched on or off) — a host
+        comparison, no device traffic."""
+        b, dev, opt = plan["batch"], plan["dev"], self.opt
+        if b.rx.parts > 1:
+            return False
+        gkey = (id(opt.param_groups), len(opt.param_groups), sum(len(g["params"]) for g in opt.param_groups))
+        if plan.get("apply_gkey") != gkey:
+            plan["apply_gkey"] = gkey
+            plan["apply_groups"], plan["apply_gidx"] = self._apply_groups(plan["comp_params"])
+        groups = plan["apply_groups"]
+        hypers = [(float(g["lr"]), float(g["momentum"]), float(g["dampening"]), float(g["weight_decay"]),
+                   bool(g["nesterov"])) for g in groups]
+        dense = [h[3] != 0 for h in hypers]
+        use_buf = [h[3] != 0 and h[1] != 0 for h in hypers]
+        f32, state = torch.float32, opt.state
+        rows, fresh = [], []
+        for p, gi, off, numel in zip(plan["comp_params"], plan["apply_gidx"], b.offsets, b.numels):
+            if not (p.is_cuda and p.dtype == f32 and p.device == dev and p.is_contiguous()):
+                return False
+            bptr, first = 0, 0
+            if use_buf[gi]:   # the momentum buffer as DGCSGD._fused_group creates it
+                buf = state[p].get("momentum_buffer") if p in state else None
+                if buf is None:
+                    first = 1
+                    fresh.append((len(rows), p))
+                elif not (torch.is_tensor(buf) and buf.is_cuda and buf.dtype == f32 and buf.device == dev
+                          and buf.is_contiguous() and buf.numel() == numel):
+                    return False
+                else:
+                    bptr = buf.data_ptr()
+            rows.append([p.data_ptr(), bptr, off, numel, first, gi, dense[gi]])
+        for i, p in fresh:
+            buf = state[p]["momentum_buffer"] = torch.empty_like(p.data)
+            rows[i][1] = buf.data_ptr()
+        try:
+            table = plan.get("apply_table")
+            if table is None:
+                table = plan["apply_table"] = _lib.ApplyTable(dev)
+            table.update([tuple(r) for r in rows])
+            b.apply(table, hypers)
+        except Exception:
+            for _, p in fresh:   # refused before anything ran: no uninitialised buffer stays behind
+                del state[p]["momentum_buffer"]
+            raise
+        _glue().release_grads(plan["comp_params"])
+        return True
 
     def release_grads(self, param_groups):
         """zero_grad(set_to_none=True): every gradient of the wrapped optimizer's params

@@ -73,13 +73,20 @@ class _DistributedOptimizer(torch.optim.Optimizer):
         if batch == "auto":
             from dgc.horovod import batched
             batch = batched.auto(compression, named_parameters, op)
+        self._apply_mode = batch == "apply"   # the compressed tensors stepped from the gathered entries
         if batch:
             from dgc.horovod import batched
             if not batched.supported(compression):
                 raise ValueError("batch=True needs a DGCCompressor driving a DGCSGDMemory with strided sampling "
                                  "and no gradient clipping other than a local dgc.clip_grad function")
+            if self._apply_mode:
+                from dgc.optim import DGCSGD
+                if not isinstance(self, DGCSGD):
+                    raise ValueError(f"batch='apply' applies dgc.optim.DGCSGD's step from the gathered entries; "
+                                     f"a {type(self).__name__} runs with batch=True")
             self._batched = batched.BatchedStep(compression, named_parameters,
-                                                fill="sparse" if batch == "sparse" else "inline")
+                                                fill="sparse" if batch == "sparse" else "inline",
+                                                apply=self if self._apply_mode else None)
         if comm.size() > 1 or os.environ.get("HOROVOD_ELASTIC") == "1":
             self._register_hooks()
 
@@ -164,11 +171,16 @@ class _DistributedOptimizer(torch.optim.Optimizer):
         return hook
 
     def synchronize(self):
+        """Exchanges every gradient and leaves the result in ``p.grad`` (batch="apply" too:
+        whoever calls this wants the gradients; only ``step()``'s own call applies)."""
+        self._synchronize()
+
+    def _synchronize(self, apply=False):
         if self._batched is not None:
             try:
                 if self._requires_update:
                     # one grouped compress -> allgather -> decompress (+ one dense allreduce)
-                    self._batched.step(self._order)
+                    self._batched.step(self._order, apply=apply)
             finally:   # a step that raised (a corrupted payload reported) leaves the hooks re-armed
                 self._reset_cells()
                 self._order.clear()
@@ -203,7 +215,8 @@ class _DistributedOptimizer(torch.optim.Optimizer):
                               "optimizer.synchronize(). This can cause training slowdown. You may want to "
                               "consider using optimizer.skip_synchronize() context if you use "
                               "optimizer.synchronize() in your code.")
-            self.synchronize()
+            # batch="apply": this call synchronizes and no closure wants the gradients
+            self._synchronize(apply=self._apply_mode and closure is None)
         self._synchronized = False
         return super(self.__class__, self).step(closure)
 
@@ -242,7 +255,16 @@ def DistributedOptimizer(optimizer, named_parameters=None, compression=Compressi
     and so the weights are those of the per-tensor path. ``batch="sparse"`` also
     replaces decompress's dense ``zero_()`` by a re-zero of the previous step's entries
     when the gradients were not written in between (see dgc/horovod/batched.py for what
-    it cannot see)."""
+    it cannot see).
+
+    ``batch="apply"`` (a ``dgc.optim.DGCSGD`` around fp32 parameters, at most 8 parameter
+    groups holding compressed tensors) is ``batch=True`` whose ``step()`` does not decompress
+    the compressed tensors into ``p.grad``: their update is applied from the gathered
+    entries (``dgc_apply_packed_multi``), the weights and the optimizer state are the same
+    bit for bit, and those parameters have ``p.grad = None`` afterwards. A step given a
+    closure, or under ``skip_synchronize()`` after an explicit ``synchronize()``, or whose
+    exchange is split or has no compressed tensor, decompresses as ``batch=True`` does
+    (``BatchedStep.apply_steps`` / ``dense_steps`` count both kinds)."""
     if op == Adasum and comm.size() > 1:
         raise NotImplementedError("Adasum is not part of the DGC path (dgc/horovod/optimizer.py:197-367)")
     if batch and op != Average:

@@ -26,6 +26,8 @@
  *   dgc_sgd_step          DGCSGD.step (weight-decay momentum + update) dgc/optim/sgd.py:42-68
  *   dgc_apply_packed      the same step of one parameter from the gathered payload's entries
  *                         (the decompressed gradient never read as a dense tensor)
+ *   dgc_apply_packed_multi  the same for the tensors of a batch, one hyper-parameter set per
+ *                         parameter group (DistributedOptimizer(batch="apply"))
  *   dgc_compensate16, dgc_mask_indices16, dgc_widen16, dgc_decompress16
  *                         the same memory / decompress for bf16 / fp16 parameters
  *                         (dgc/memory.py:43-77, dgc/compression.py:179-194 on a
@@ -527,6 +529,62 @@ int dgc_apply_packed(const void* payload, int32_t world, int64_t rank_stride, in
                      int32_t idtype, float* acc, float* param, float* buf, int32_t first, int64_t n, float lr,
                      float momentum, float dampening, float weight_decay, int32_t nesterov, void* ws, size_t ws_bytes,
                      void* stream);
+/* K7 sparse, multi-tensor: dgc_apply_packed for `count` fp32 parameter tensors laid side by
+ * side in one flat index space (a batch's layout, dgc_batch_desc: the payload carries FLAT
+ * indices), each with the hyper-parameters of its parameter group — the batched
+ * DistributedOptimizer's compressed tensors stepped from the gathered entries, with no dense
+ * gradient written or read. At most three launches, whatever `count` and `groups` are.
+ *
+ * table: `count` rows in DEVICE memory, owned and kept by the caller, sorted by offset,
+ * their [offset, offset + numel) ranges disjoint and inside [0, flat_numel). Build it when
+ * the layout is built and upload it again only when a row changes (`first` turning 0 after a
+ * buffer's first step, a reallocated parameter, a group's weight decay switched on or off:
+ * block0). The call copies nothing to the device and never synchronises. A row: */
+typedef struct dgc_apply_row {
+    float* param;             /* the tensor: numel contiguous fp32 elements (4-B aligned;   */
+                              /*   16-B aligned tensors take the vector path)               */
+    float* momentum_buffer;   /* DGCSGD's state[p]["momentum_buffer"], same shape; read and */
+                              /*   written only when the row's group has weight_decay != 0  */
+                              /*   and momentum != 0 (else it may be NULL)                  */
+    int64_t offset;           /* flat index of the tensor's element 0                       */
+    int64_t numel;            /* elements (0: a row no entry matches, no block)             */
+    int64_t block0;           /* first block of the tensor in the dense pass: the sum of    */
+                              /*   ceil(numel / 4096) over the rows before it whose group   */
+                              /*   has weight_decay != 0 (rows of other groups add nothing) */
+    int32_t first;            /* 1: the momentum buffer is created on this step (buf = wd*p)*/
+    int32_t group;            /* index into `hypers`, 0 <= group < groups                   */
+} dgc_apply_row;              /* 48 bytes, no padding */
+/* One parameter group's hyper-parameters (host array of `groups` <= 8, read at every call). */
+typedef struct dgc_apply_hyper {
+    float lr, momentum, dampening, weight_decay;
+    int32_t nesterov;
+} dgc_apply_hyper;
+/* dense_blocks: the dense pass's grid = the sum of ceil(numel / 4096) over the rows whose
+ * group has weight_decay != 0 (0 when none has).
+ * Precondition: acc[0..flat_numel) holds exactly dgc_scatter_packed's result of `payload`
+ * (same world / rank_stride / capacity / dtypes, n = flat_numel, the 1/W scale) onto +0.0.
+ * rank_stride may exceed dgc_payload_layout's (the batched step's dense tail rides behind the
+ * entries). Per entry: an index outside [0, flat_numel) is skipped before any access (the
+ * scatter flagged it); otherwise its row is found by binary search, its slot of acc taken
+ * with an atomic exchange against +0.0, and a +0.0 slot skipped, as in dgc_apply_packed. An
+ * in-range index inside no row (a padding gap; this library emits none) has its slot
+ * exchanged out and dropped. A group with weight decay takes dgc_apply_packed's three phases
+ * over its tensors (stash, the dense g = +0.0 pass over param (+ buf), fix-up); one without
+ * takes p = fma(g, -lr, p) at the entries and gets no block of the dense pass.
+ * Postcondition: acc is +0.0 everywhere; every param (and momentum buffer in use) is bit for
+ * bit what dgc_sgd_step would have left with acc's slice as its gradient.
+ * ws: dgc_apply_packed_multi_workspace bytes (4 B per gathered slot, rounded up to 256),
+ * 256-B aligned, needed when any group has weight_decay != 0 (else it may be NULL).
+ * Every argument is checked before the first launch (a refusal leaves every tensor
+ * untouched): a null payload, acc, table or hypers; world outside 1..64; an unsupported
+ * dtype; rank_stride below the layout; count < 1, flat_numel < 1; groups outside 1..8; a
+ * negative or NaN lr; dense_blocks outside [0, 2^31); a missing, small or misaligned ws. */
+size_t dgc_apply_packed_multi_workspace(int32_t world, int64_t capacity);
+int dgc_apply_packed_multi(const void* payload, int32_t world, int64_t rank_stride, int64_t capacity,
+                           int32_t vdtype, int32_t idtype, float* acc, int64_t flat_numel,
+                           const dgc_apply_row* table, int32_t count, int64_t dense_blocks,
+                           const dgc_apply_hyper* hypers, int32_t groups, void* ws, size_t ws_bytes,
+                           void* stream);
 /* K7-16: the same for bf16 / fp16 parameters (dtype DGC_BF16 / DGC_F16; params, grads,
  * bufs 16-bit arrays of that dtype): every op rounds to the dtype as the reference's
  * torch-CPU ops on a 16-bit tensor do — alpha rounded to the dtype; `add(alpha)` rounds
