@@ -140,7 +140,8 @@ __device__ void nth_adjust_heap(QP q, int64_t hole, int64_t n, uint64_t v) {
 }
 
 // std::__heap_select(q, q + mid, q + n), then iter_swap(q, q + nth): the depth-limit
-// exit of std::__introselect. Single thread; reached only by adversarial inputs.
+// exit of std::__introselect. Single thread; tests/killer.py builds the inputs that reach it
+// (tests/test_gpu_killer.py runs them through every phase's copy of this exit).
 template <class QP>
 __device__ void nth_heap_select(QP q, int64_t mid, int64_t n, int64_t nth) {
     if (mid >= 2) {

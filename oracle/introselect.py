@@ -161,18 +161,27 @@ def _sort_heap(key, pos, f, l):
 
 
 # ------------------------------------------------------------------ entry points
-def nth_element(key, pos, nth):
-    """std::nth_element(queue, queue + nth, queue + n, comp), in place."""
+def nth_element(key, pos, nth, trace=None):
+    """std::nth_element(queue, queue + nth, queue + n, comp), in place.
+
+    ``trace``: a list that receives ``(f, l, depth)`` for every partition step (the depth
+    left when the step starts) and, last, the exit: ``("heap", f, l)`` for the depth-limit
+    heap select or ``("insertion", f, l)`` (tests/killer.py records the same from its
+    scalar restatement)."""
     f, l = 0, key.size
     if f == l or nth == l:
         return
     depth = 2 * _lg(l - f)
     while l - f > 3:
         if depth == 0:
+            if trace is not None:
+                trace.append(("heap", f, l))
             _heap_select(key, pos, f, nth + 1, l)
             key[f], key[nth] = key[nth], key[f]
             pos[f], pos[nth] = pos[nth], pos[f]
             return
+        if trace is not None:
+            trace.append((f, l, depth))
         depth -= 1
         _median_to_first(key, pos, f, f + 1, f + (l - f) // 2, l - 1)
         cut = _partition(key, pos, f, l)
@@ -180,6 +189,8 @@ def nth_element(key, pos, nth):
             f = cut
         else:
             l = cut
+    if trace is not None:
+        trace.append(("insertion", f, l))
     _insertion_sort(key, pos, f, l)
 
 
