@@ -19,6 +19,11 @@
 // HBM: the dense write (4 B/elem) plus the sparse reads W*k*(vb+ib) and one
 // scattered store per distinct index. Untouched slots come out +0.0 exactly as
 // zero_() * (1/W).
+//
+// K6-16 (dgc_fill_zero16 + dgc_scatter_split16): the same several-runs scatter onto a
+// bf16 / fp16 gradient for the split exchange of 16-bit parameters — the kernels take the
+// output as a template parameter (Out<OD>): a rounding to the dtype after every add and
+// after the scale, one 2-byte store per index, 2 B/elem of fill.
 #include "dgc_common.hpp"
 
 #include <mutex>
@@ -99,8 +104,31 @@ __device__ __forceinline__ void flag_count(const DecWS& w) {
 template <int VD>
 __device__ __forceinline__ float load_val(const void* p, long long e) {
     if (VD == DGC_F16) return (float)((const DGC_GLB _Float16*)p)[e];   // typed: global_ loads; exact widening
+    if (VD == DGC_BF16) return bf16_to_f32(((const DGC_GLB uint16_t*)p)[e]);   // (K6-16's wire only)
     return ((const DGC_GLB float*)p)[e];
 }
+
+// What the scatter writes. K6 (OD = DGC_F32): fp32 words, every add and the scale rounded
+// to fp32 by the instruction itself. K6-16 (OD = DGC_BF16 / DGC_F16, the split exchange of
+// 16-bit parameters): 2-byte elements, and rd() after every op — values.type(dtype), each
+// index_put_ add and the mul_(1/W) round to the gradient's dtype as ATen's ops on a 16-bit
+// tensor do (dgc/compression.py:186-194; k_scatter_packed16 + k_scale16 in half.hip).
+// kExactWindow: a split phase writes exactly the indices inside its window (K6 rounds the
+// window down to whole super-chunks and leaves the rest to the next phase).
+template <int OD>
+struct Out {
+    using T = uint16_t;
+    static constexpr bool kExactWindow = true;
+    static __device__ __forceinline__ float rd(float x) { return round16<OD>(x); }
+    static __device__ __forceinline__ T pack(float x) { return f32_to_h16<OD>(x); }
+};
+template <>
+struct Out<DGC_F32> {
+    using T = float;
+    static constexpr bool kExactWindow = false;
+    static __device__ __forceinline__ float rd(float x) { return x; }
+    static __device__ __forceinline__ T pack(float x) { return x; }
+};
 
 template <int ID>
 __device__ __forceinline__ long long load_idx(const void* p, long long e) {
@@ -326,7 +354,7 @@ __global__ void __launch_bounds__(kRegroupThreads) k_regroup(DecWS w, RunSrc rs,
         const long long i = load_idx<ID>(run.idx, e2);
         if (i < 0 || i >= n) continue;
         const uint32_t pos = atomicAdd(&cur[i >> 12], 1u);
-        if (VD == DGC_F16)
+        if (VD != DGC_F32)   // fp16 / bf16: the 2 bytes as they are
             reinterpret_cast<__half*>(sv)[pos] = reinterpret_cast<const __half*>(run.vals)[e2];
         else
             reinterpret_cast<float*>(sv)[pos] = reinterpret_cast<const float*>(run.vals)[e2];
@@ -348,9 +376,9 @@ __global__ void __launch_bounds__(kRegroupThreads) k_regroup(DecWS w, RunSrc rs,
 // atomics. Then * (1/W), and the touched elements are stored.
 constexpr int kTileStage = 1024;
 
-template <int VD, int ID>
-__device__ void tile_chunk(const DecWS& w, const RunSrc& rs, float* __restrict__ grad, int64_t n, float scale,
-                           int64_t c) {
+template <int VD, int ID, int OD>
+__device__ void tile_chunk(const DecWS& w, const RunSrc& rs, typename Out<OD>::T* __restrict__ grad, int64_t n,
+                           float scale, int64_t c) {
     __shared__ int soff[kTileStage];
     __shared__ float sval[kTileStage];
     __shared__ int roff[kMaxRuns + 1];
@@ -382,6 +410,11 @@ __device__ void tile_chunk(const DecWS& w, const RunSrc& rs, float* __restrict__
     }
     __syncthreads();
     const int total = roff[nr];
+    long long wlo = 0, whi = LLONG_MAX;   // the phase's index window (K6-16; see k_scatter_waves)
+    if (Out<OD>::kExactWindow && rs.parts > 1) {
+        if (rs.ready > 1) wlo = rs.landed_below(rs.ready - 2);
+        if (rs.ready < rs.parts) whi = rs.landed_below(rs.ready - 1);
+    }
     float a[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) a[j] = 0.f;
@@ -394,13 +427,15 @@ __device__ void tile_chunk(const DecWS& w, const RunSrc& rs, float* __restrict__
             const long long e = rb0[r] + (t0 + t - roff[r]);
             const long long off = load_idx<ID>(ridx[r], e) - base;
             soff[t] = (off >= 0 && off < kChunk) ? (int)off : -1;
-            sval[t] = load_val<VD>(rval[r], e);
+            if (Out<OD>::kExactWindow && (off + base < wlo || off + base >= whi)) soff[t] = -2;   // another phase's
+            sval[t] = Out<OD>::rd(load_val<VD>(rval[r], e));
         }
         __syncthreads();
         for (int t = 0; t < m; ++t) {
             const int off = __builtin_amdgcn_readfirstlane(soff[t]);   // uniform: scalar branches
             if (off < 0) {
-                if (tid == 0) atomicOr(w.status, 2);   // only an unsorted run lands outside its chunk
+                // only an unsorted run lands outside its chunk (-2: inside it, another phase's)
+                if (tid == 0 && (!Out<OD>::kExactWindow || off == -1)) atomicOr(w.status, 2);
                 continue;
             }
             if (((off >> 8) & 3) != wave) continue;
@@ -410,14 +445,14 @@ __device__ void tile_chunk(const DecWS& w, const RunSrc& rs, float* __restrict__
                 touched |= 1u << slot;
 #pragma unroll
                 for (int j = 0; j < 16; ++j)
-                    if (j == slot) a[j] = __fadd_rn(a[j], v);
+                    if (j == slot) a[j] = Out<OD>::rd(__fadd_rn(a[j], v));
             }
         }
         __syncthreads();
     }
     if (scale != 1.0f) {
 #pragma unroll
-        for (int j = 0; j < 16; ++j) a[j] = __fmul_rn(a[j], scale);
+        for (int j = 0; j < 16; ++j) a[j] = Out<OD>::rd(__fmul_rn(a[j], scale));
     }
     if (!touched) return;
     const long long len = n - base < kChunk ? n - base : kChunk;
@@ -426,7 +461,7 @@ __device__ void tile_chunk(const DecWS& w, const RunSrc& rs, float* __restrict__
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const long long e = (long long)(u * kBlock + tid) * 4 + j;
-            if (e < len && ((touched >> (4 * u + j)) & 1u)) grad[base + e] = a[4 * u + j];
+            if (e < len && ((touched >> (4 * u + j)) & 1u)) grad[base + e] = Out<OD>::pack(a[4 * u + j]);
         }
 }
 
@@ -515,9 +550,11 @@ __device__ __forceinline__ void wave_sync_lds() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int VD, int ID>
+template <int VD, int ID, int OD>
 __global__ void __launch_bounds__(kBlock)
-k_scatter_waves(DecWS w, RunSrc rs, float* __restrict__ grad, int64_t n, float scale, int m, int gran) {
+k_scatter_waves(DecWS w, RunSrc rs, typename Out<OD>::T* __restrict__ grad, int64_t n, float scale, int m, int gran) {
+    using O = Out<OD>;
+    if (OD != DGC_F32) gran = 0;   // K6-16 stores 2-byte elements only (the granule path below is fp32's layout)
     // per-wave duplicate filter: one bit per (offset mod 4096) of the super-chunk; and
     // per-granule counts of the entries to store (64-B granule, mod kGranules)
     __shared__ uint32_t dup_bits[kSegWaves][kChunk / 32];
@@ -533,11 +570,22 @@ k_scatter_waves(DecWS w, RunSrc rs, float* __restrict__ grad, int64_t n, float s
     // exchange, parts < ready landed — those every index of which has landed and that
     // no earlier phase took (landed_below is non-decreasing in the part)
     const int64_t nsc = ceil_div(w.nchunks, (int64_t)m), span = (int64_t)m * kChunk;
+    // K6-16 (O::kExactWindow) cuts the window at the index, not at the super-chunk: the
+    // super-chunk a bound falls into is walked by both phases, each taking its side
     int64_t lo = 0, hi = nsc;
+    long long wlo = 0, whi = LLONG_MAX;
     if (rs.parts > 1) {
         const int p = rs.ready - 1;
-        if (p > 0) lo = rs.landed_below(p - 1) / span;
-        if (p < rs.parts - 1) hi = rs.landed_below(p) / span;
+        if constexpr (O::kExactWindow) {
+            if (p > 0) wlo = rs.landed_below(p - 1);
+            if (p < rs.parts - 1) whi = rs.landed_below(p);
+            lo = wlo / span;
+            hi = whi / span;
+            if (whi < nsc * span && whi % span) ++hi;
+        } else {
+            if (p > 0) lo = rs.landed_below(p - 1) / span;
+            if (p < rs.parts - 1) hi = rs.landed_below(p) / span;
+        }
         lo = lo < 0 ? 0 : (lo > nsc ? nsc : lo);
         hi = hi < lo ? lo : (hi > nsc ? nsc : hi);
     }
@@ -604,14 +652,15 @@ k_scatter_waves(DecWS w, RunSrc rs, float* __restrict__ grad, int64_t n, float s
             v[j] = 0.f;
             if (T[j] <= 64 && lane < T[j]) {
                 const long long e = e0 + (lane - first);
-                v[j] = load_val<VD>(reinterpret_cast<const void*>(pv), e);
+                v[j] = O::rd(load_val<VD>(reinterpret_cast<const void*>(pv), e));
                 const long long i = load_idx<ID>(reinterpret_cast<const void*>(pi), e);
                 const long long lo_i = (sc0 + j) * m * (long long)kChunk;
                 const long long hi_i = (sc0 + j + 1) * m < w.nchunks ? (sc0 + j + 1) * m * (long long)kChunk : n;
-                if (i >= lo_i && i < hi_i)
-                    off[j] = (int)(i - lo_i);
-                else
+                if (i >= lo_i && i < hi_i) {
+                    if (!O::kExactWindow || (i >= wlo && i < whi)) off[j] = (int)(i - lo_i);
+                } else {
                     atomicOr(w.status, 2);   // only an unsorted run lands outside its chunks
+                }
             }
         }
 #pragma unroll
@@ -640,7 +689,7 @@ k_scatter_waves(DecWS w, RunSrc rs, float* __restrict__ grad, int64_t n, float s
                         if (q < lane)
                             head = false;
                         else
-                            a = __fadd_rn(a, vq);
+                            a = O::rd(__fadd_rn(a, vq));
                     }
                 }
             } else {
@@ -655,14 +704,14 @@ k_scatter_waves(DecWS w, RunSrc rs, float* __restrict__ grad, int64_t n, float s
             // inside grad: with an unaligned grad, granules straddle chunk edges
             const long long c_lo = (sc0 + j) * m * (long long)kChunk;
             const long long c_hi = (sc0 + j + 1) * m * (long long)kChunk < n ? (sc0 + j + 1) * m * (long long)kChunk : n;
-            float* dst = grad + c_lo + off[j];
+            typename O::T* dst = grad + c_lo + off[j];
             const uintptr_t g = reinterpret_cast<uintptr_t>(dst) & ~(uintptr_t)63;
             const uint32_t gslot = (uint32_t)(g >> 6) & (kGranules - 1);
             if (gran && head) atomicAdd(&gcnt[gslot], 1u);
             if (gran) wave_sync_lds();
             const bool alone = gran && head && gcnt[gslot] == 1 && g >= reinterpret_cast<uintptr_t>(grad + c_lo) &&
                                g + 64 <= reinterpret_cast<uintptr_t>(grad + c_hi);
-            const float val = scale != 1.0f ? __fmul_rn(a, scale) : a;
+            const float val = scale != 1.0f ? O::rd(__fmul_rn(a, scale)) : a;
             if (alone) {
                 const int pos = (int)((reinterpret_cast<uintptr_t>(dst) - g) >> 2);
                 DGC_GLB f4v* g4 = (DGC_GLB f4v*)g;
@@ -673,7 +722,7 @@ k_scatter_waves(DecWS w, RunSrc rs, float* __restrict__ grad, int64_t n, float s
                     g4[q] = v;
                 }
             } else if (head) {
-                *dst = val;
+                *dst = O::pack(val);
             }
             if (gran) {
                 wave_sync_lds();
@@ -684,13 +733,13 @@ k_scatter_waves(DecWS w, RunSrc rs, float* __restrict__ grad, int64_t n, float s
 }
 
 // The queued super-chunks, one 4096-element chunk per workgroup iteration.
-template <int VD, int ID>
+template <int VD, int ID, int OD>
 __global__ void __launch_bounds__(kBlock)
-k_scatter_overflow(DecWS w, RunSrc rs, float* __restrict__ grad, int64_t n, float scale, int m) {
+k_scatter_overflow(DecWS w, RunSrc rs, typename Out<OD>::T* __restrict__ grad, int64_t n, float scale, int m) {
     const int64_t total = (int64_t)(*w.ovf_cnt) * m;
     for (int64_t q = blockIdx.x; q < total; q += gridDim.x) {
         const int64_t c = (int64_t)w.ovf_list[q / m] * m + q % m;
-        if (c < w.nchunks) tile_chunk<VD, ID>(w, rs, grad, n, scale, c);
+        if (c < w.nchunks) tile_chunk<VD, ID, OD>(w, rs, grad, n, scale, c);
         __syncthreads();
     }
 }
@@ -768,35 +817,42 @@ static int launch_clear(const RunSrc& prev, const DecWS& w, float* grad, int64_t
 // prev: the previous payload (kZeroPrev only). A phase of a split exchange (rs.parts >
 // 1: the runs of part rs.ready - 1 just landed) bounds and regroups only those runs and
 // scatters the super-chunks whose indices have all landed; zmode applies to phase 0.
-template <int VD, int ID>
-static int run_scatter(const DecWS& w, const RunSrc& rs, float* grad, int64_t n, float scale, int max_runs,
-                       int zmode, int64_t entries, int64_t run_cap, int runs, hipStream_t s,
+// OD: the output's dtype (Out<OD>). The 16-bit outputs exist for the split phases only
+// (dgc_scatter_split16: kZeroNone, several runs).
+template <int VD, int ID, int OD = DGC_F32>
+static int run_scatter(const DecWS& w, const RunSrc& rs, typename Out<OD>::T* grad, int64_t n, float scale,
+                       int max_runs, int zmode, int64_t entries, int64_t run_cap, int runs, hipStream_t s,
                        const RunSrc* prev = nullptr) {
     if (w.nchunks > 0x7FFFFFFFLL) DGC_FAIL(DGC_ERR_INVALID, "dgc_decompress: n too large");
     const bool split = rs.payload && rs.parts > 1;
     const int part = split ? rs.ready - 1 : 0;
+    if (OD != DGC_F32 && (!split || zmode != kZeroNone))
+        DGC_FAIL(DGC_ERR_INVALID, "dgc_decompress: a 16-bit output takes the split phases only");
     // status, the overflow queue count and the unsorted flags are reset before any
     // kernel of this call can set them: by the dense fill's (or the sparse re-zero's)
     // first block, or memsets; a later phase of a split exchange only restarts the
     // overflow queue (the previous phase's queued super-chunks are done)
     if (part > 0) {
         DGC_HIP(hipMemsetAsync(w.ovf_cnt, 0, sizeof(int32_t), s));
-    } else if (zmode == kZeroPrev) {
-        DGC_TRY(launch_clear<ID>(*prev, w, grad, n, s));
-    } else if (zmode == kZeroDense) {
-        DGC_TRY(fill_zero(grad, n, s, status_words(w)));
     } else if (zmode == kZeroNone) {
         if (w.sort_cap) DGC_HIP(hipMemsetAsync(w.unsorted, 0, kMaxRuns * sizeof(int32_t), s));
         DGC_HIP(hipMemsetAsync(w.status, 0, sizeof(int32_t), s));
         DGC_HIP(hipMemsetAsync(w.ovf_cnt, 0, sizeof(int32_t), s));
     }
-    if (runs == 1) {   // a thread per entry
-        if (entries > 0) {
-            hipLaunchKernelGGL((k_scatter_single<VD, ID>), dim3((unsigned)ceil_div(4 * entries, (int64_t)kBlock)),
-                               dim3(kBlock), 0, s, w, rs, grad, n, scale);
-            DGC_LAUNCHED();
+    if constexpr (OD == DGC_F32) {
+        if (part == 0 && zmode == kZeroPrev) {
+            DGC_TRY(launch_clear<ID>(*prev, w, grad, n, s));
+        } else if (part == 0 && zmode == kZeroDense) {
+            DGC_TRY(fill_zero(grad, n, s, status_words(w)));
         }
-        return DGC_OK;
+        if (runs == 1) {   // a thread per entry
+            if (entries > 0) {
+                hipLaunchKernelGGL((k_scatter_single<VD, ID>), dim3((unsigned)ceil_div(4 * entries, (int64_t)kBlock)),
+                                   dim3(kBlock), 0, s, w, rs, grad, n, scale);
+                DGC_LAUNCHED();
+            }
+            return DGC_OK;
+        }
     }
     const unsigned bx = (unsigned)grid_for(run_cap + 1, kBlock, kMaxGrid / 2);
     const int ystep = split ? rs.parts : 1, yruns = split ? rs.world : max_runs;
@@ -817,10 +873,10 @@ static int run_scatter(const DecWS& w, const RunSrc& rs, float* grad, int64_t n,
     const dim3 grid((unsigned)ceil_div(nsc, (int64_t)kSegWaves * kSCB * (split ? rs.parts : 1)));
     // whole-granule stores pay for their LDS bookkeeping from ~24 entries per chunk on
     // (measured at 1B: W = 8 scatter 0.39 -> 0.33 ms; W = 2 and 4 a few % slower with it)
-    const int gran = per_chunk >= 24.0 ? 1 : 0;
-    hipLaunchKernelGGL((k_scatter_waves<VD, ID>), grid, dim3(kBlock), 0, s, w, rs, grad, n, scale, m, gran);
+    const int gran = OD == DGC_F32 && per_chunk >= 24.0 ? 1 : 0;
+    hipLaunchKernelGGL((k_scatter_waves<VD, ID, OD>), grid, dim3(kBlock), 0, s, w, rs, grad, n, scale, m, gran);
     DGC_LAUNCHED();
-    hipLaunchKernelGGL((k_scatter_overflow<VD, ID>), dim3(512), dim3(kBlock), 0, s, w, rs, grad, n, scale, m);
+    hipLaunchKernelGGL((k_scatter_overflow<VD, ID, OD>), dim3(512), dim3(kBlock), 0, s, w, rs, grad, n, scale, m);
     DGC_LAUNCHED();
     return DGC_OK;
 }
@@ -839,9 +895,10 @@ static int dispatch_scatter(int vd, int id, const DecWS& w, const RunSrc& rs, fl
     DGC_FAIL(DGC_ERR_DTYPE, "dgc_decompress: unsupported value/index dtype (%d, %d)", vd, id);
 }
 
-static int check_common(int vd, int id, float* grad, int64_t n, void* ws, size_t ws_bytes, int runs,
-                        int64_t sort_cap = 0) {
-    if ((vd != DGC_F32 && vd != DGC_F16) || (id != DGC_I64 && id != DGC_I32))
+// wire_bf16: the call also takes bf16 wire values (the 16-bit split scatter)
+static int check_common(int vd, int id, const void* grad, int64_t n, void* ws, size_t ws_bytes, int runs,
+                        int64_t sort_cap = 0, bool wire_bf16 = false) {
+    if ((vd != DGC_F32 && vd != DGC_F16 && !(wire_bf16 && vd == DGC_BF16)) || (id != DGC_I64 && id != DGC_I32))
         DGC_FAIL(DGC_ERR_DTYPE, "dgc_decompress: unsupported value/index dtype (%d, %d)", vd, id);
     if (!grad || n < 1) DGC_FAIL(DGC_ERR_INVALID, "dgc_decompress: null grad or n < 1");
     if (runs < 1 || runs > kMaxRuns) DGC_FAIL(DGC_ERR_INVALID, "dgc_decompress: 1..%d runs supported", kMaxRuns);
@@ -1020,10 +1077,10 @@ static RunSrc split_src(const void* gathered, int32_t world, int parts, int read
 }
 
 static int check_split(const void* gathered, int32_t world, int parts, int64_t capacity, int vd, int id,
-                       const char* fn) {
+                       const char* fn, bool wire_bf16 = false) {
     if (!gathered || world < 1 || parts < 2 || parts > kMaxParts || capacity < 0 || world * parts > kMaxRuns)
         DGC_FAIL(DGC_ERR_INVALID, "%s: null buffer, parts outside 2..%d or world * parts > %d", fn, kMaxParts, kMaxRuns);
-    if ((vd != DGC_F32 && vd != DGC_F16) || (id != DGC_I64 && id != DGC_I32))
+    if ((vd != DGC_F32 && vd != DGC_F16 && !(wire_bf16 && vd == DGC_BF16)) || (id != DGC_I64 && id != DGC_I32))
         DGC_FAIL(DGC_ERR_DTYPE, "%s: unsupported value/index dtype (%d, %d)", fn, vd, id);
     return DGC_OK;
 }
@@ -1053,6 +1110,44 @@ int clear_split(const void* prev, int32_t world, int parts, int64_t capacity, in
     const DecWS w = carve_dec(ws, n, world * parts, pc);
     const RunSrc pr = split_src(prev, world, parts, parts, pbytes, pc, voff, ioff, nullptr);
     return id == DGC_I32 ? launch_clear<DGC_I32>(pr, w, grad, n, s) : launch_clear<DGC_I64>(pr, w, grad, n, s);
+}
+
+// K6-16: phase `part` of the split decompress onto a bf16 / fp16 gradient that holds +0
+// (dgc_fill_zero16 before phase 0, which resets the status words). The phases, their
+// windows, the bounds, the regroup and both scatter paths are scatter_split's; the
+// kernels round to the dtype after every op and store 2-byte elements (Out<OD>).
+template <int OD, int VD>
+static int scatter16_id(int id, const DecWS& w, const RunSrc& rs, uint16_t* grad, int64_t n, float scale, int runs,
+                        int64_t pc, hipStream_t s) {
+    const int64_t entries = (int64_t)runs * pc;
+    return id == DGC_I32 ? run_scatter<VD, DGC_I32, OD>(w, rs, grad, n, scale, runs, kZeroNone, entries, pc, runs, s)
+                         : run_scatter<VD, DGC_I64, OD>(w, rs, grad, n, scale, runs, kZeroNone, entries, pc, runs, s);
+}
+
+template <int OD>
+static int scatter16_vd(int vd, int id, const DecWS& w, const RunSrc& rs, uint16_t* grad, int64_t n, float scale,
+                        int runs, int64_t pc, hipStream_t s) {
+    if (vd == DGC_F32) return scatter16_id<OD, DGC_F32>(id, w, rs, grad, n, scale, runs, pc, s);
+    if (vd == DGC_F16) return scatter16_id<OD, DGC_F16>(id, w, rs, grad, n, scale, runs, pc, s);
+    return scatter16_id<OD, DGC_BF16>(id, w, rs, grad, n, scale, runs, pc, s);
+}
+
+int scatter_split16(const void* gathered, int32_t world, int parts, int part, int64_t capacity, int vd, int id,
+                    void* grad, int od, int64_t n, float scale, void* ws, size_t ws_bytes, hipStream_t s) {
+    const char* fn = "dgc_scatter_split16";
+    if (od != DGC_BF16 && od != DGC_F16) DGC_FAIL(DGC_ERR_DTYPE, "%s: grad dtype must be DGC_BF16 or DGC_F16", fn);
+    DGC_TRY(check_split(gathered, world, parts, capacity, vd, id, fn, true));
+    if (part < 0 || part >= parts) DGC_FAIL(DGC_ERR_INVALID, "%s: part %d outside 0..%d", fn, part, parts - 1);
+    if (!grad || n < 1) DGC_FAIL(DGC_ERR_INVALID, "%s: null grad or n < 1", fn);
+    if (reinterpret_cast<uintptr_t>(grad) & 1) DGC_FAIL(DGC_ERR_INVALID, "%s: grad must be 2-B aligned", fn);
+    int64_t pc, voff, ioff;
+    const int64_t pbytes = split_layout(capacity, parts, vd, id, &pc, &voff, &ioff);
+    DGC_TRY(check_common(vd, id, grad, n, ws, ws_bytes, world * parts, pc, true));
+    const DecWS w = carve_dec(ws, n, world * parts, pc);
+    const RunSrc rs = split_src(gathered, world, parts, part + 1, pbytes, pc, voff, ioff, &w);
+    uint16_t* g = static_cast<uint16_t*>(grad);
+    return od == DGC_BF16 ? scatter16_vd<DGC_BF16>(vd, id, w, rs, g, n, scale, world * parts, pc, s)
+                          : scatter16_vd<DGC_F16>(vd, id, w, rs, g, n, scale, world * parts, pc, s);
 }
 
 int decompress_packed(const void* payload, int32_t world, int64_t rank_stride, int64_t capacity, int vd,
@@ -1144,6 +1239,35 @@ int fill_zero(float* x, int64_t n, hipStream_t s, const ZeroWords& z) {
     const int64_t head = n4 * 4;
     if (head < n) {
         hipLaunchKernelGGL(k_fill_zero1, dim3(1), dim3(64), 0, s, x, head, n);
+        DGC_LAUNCHED();
+    }
+    return DGC_OK;
+}
+
+// grad.zero_() of a 16-bit tensor: +0 is all-zero bits in bf16 and fp16 too, so the body
+// is k_fill_zero's one-shot 16-B stores; the up to 7 elements before the first and after
+// the last 16-B boundary (a 2-byte-aligned view) are 2-byte stores of one small launch.
+__global__ void k_fill_zero16_edges(uint16_t* __restrict__ x, int64_t lead, int64_t tail, int64_t n) {
+    const int64_t t = threadIdx.x;
+    if (t < lead) x[t] = 0;
+    if (t >= 8 && tail + (t - 8) < n) x[tail + (t - 8)] = 0;
+}
+
+int fill_zero16(void* grad, int64_t n, hipStream_t s) {
+    if (!grad || n < 0) DGC_FAIL(DGC_ERR_INVALID, "dgc_fill_zero16: null buffer or n < 0");
+    if (reinterpret_cast<uintptr_t>(grad) & 1) DGC_FAIL(DGC_ERR_INVALID, "dgc_fill_zero16: buffer must be 2-B aligned");
+    if (n == 0) return DGC_OK;
+    uint16_t* x = static_cast<uint16_t*>(grad);
+    const int64_t lead = std::min<int64_t>(n, (int64_t)((16 - (reinterpret_cast<uintptr_t>(x) & 15)) & 15) / 2);
+    const int64_t n8 = (n - lead) / 8, tail = lead + n8 * 8;   // 16-B vectors; the first element after them
+    if (ceil_div(n8, (int64_t)kBlock) > 0x7FFFFFFFLL) DGC_FAIL(DGC_ERR_INVALID, "dgc_fill_zero16: n too large");
+    if (n8 > 0) {
+        hipLaunchKernelGGL(k_fill_zero, dim3((unsigned)ceil_div(n8, (int64_t)kBlock)), dim3(kBlock), 0, s,
+                           reinterpret_cast<float4*>(x + lead), n8, ZeroWords{}, (int)write_through(4 * n8));
+        DGC_LAUNCHED();
+    }
+    if (lead > 0 || tail < n) {   // lead <= 7, n - tail <= 7
+        hipLaunchKernelGGL(k_fill_zero16_edges, dim3(1), dim3(64), 0, s, x, lead, tail, n);
         DGC_LAUNCHED();
     }
     return DGC_OK;
@@ -1275,6 +1399,21 @@ extern "C" int dgc_scatter_split(const void* gathered, int32_t world, int32_t pa
                                  void* ws, size_t ws_bytes, void* stream) {
     return dgc::scatter_split(gathered, world, parts, part, capacity, vdtype, idtype, grad, n, scale, cleared, ws,
                               ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t dgc_decompress_split16_workspace(int64_t n, int32_t world, int32_t parts, int64_t capacity) {
+    return dgc_decompress_split_workspace(n, world, parts, capacity);   // one layout: 12 B per regrouped entry covers 2-B values
+}
+
+extern "C" int dgc_scatter_split16(const void* gathered, int32_t world, int32_t parts, int32_t part, int64_t capacity,
+                                   int32_t vdtype, int32_t idtype, void* grad, int32_t dtype, int64_t n, float scale,
+                                   void* ws, size_t ws_bytes, void* stream) {
+    return dgc::scatter_split16(gathered, world, parts, part, capacity, vdtype, idtype, grad, dtype, n, scale, ws,
+                                ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int dgc_fill_zero16(void* grad, int64_t n, void* stream) {
+    return dgc::fill_zero16(grad, n, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int dgc_clear_split(const void* prev_gathered, int32_t world, int32_t parts, int64_t capacity,

@@ -280,6 +280,9 @@ _SIGNATURES = {
     "dgc_decompress_split_workspace": (_SZ, [_I64, _I32, _I32, _I64]),
     "dgc_scatter_split": (ctypes.c_int, [_P, _I32, _I32, _I32, _I64, _I32, _I32, _P, _I64, _F, _I32, _P, _SZ, _P]),
     "dgc_clear_split": (ctypes.c_int, [_P, _I32, _I32, _I64, _I32, _I32, _P, _I64, _P, _SZ, _P]),
+    "dgc_decompress_split16_workspace": (_SZ, [_I64, _I32, _I32, _I64]),
+    "dgc_scatter_split16": (ctypes.c_int, [_P, _I32, _I32, _I32, _I64, _I32, _I32, _P, _I32, _I64, _F, _P, _SZ, _P]),
+    "dgc_fill_zero16": (ctypes.c_int, [_P, _I64, _P]),
     "dgc_fill_zero": (ctypes.c_int, [_P, _I64, _P]),
     "dgc_decompress_status": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int32), _P]),
     "dgc_decompress_bind_sink": (ctypes.c_int, [_P, _P]),

@@ -240,7 +240,8 @@ class DGCBucket(ReceiveSide):
         written. fill="sparse": a dense decompress into the previous step's untouched
         output re-zeroes only the previous entries (see ``Receiver``). A 16-bit bucket:
         zero_(), the runs in rank order (each add rounded to the dtype), the 1/W scale,
-        always dense (``HalfExchange``); its ``out`` is checked. ``aliased``: see ``step``."""
+        always dense (``HalfExchange``, or ``HalfSplitExchange`` when ``exchange_parts`` asked for
+        a split: the same bits); its ``out`` is checked. ``aliased``: see ``step``."""
         if not dense:
             self.rx.scatter(out)
             return

@@ -12,14 +12,21 @@ below the smallest such bound over the ranks (all of that index's entries have l
 so only the last part's share is exposed. The dense result is the single-collective
 decompress's bit for bit (same rank-order sums; tests/test_gpu_split.py).
 
-Used by DGCBucket / DGCBatch (fp32 parameters) at W > 1, through the ``Receiver`` both
-engines share: the back half of a step — packed payload -> allgather (``SingleExchange``
-or ``SplitExchange``; ``HalfExchange``, always one allgather, for 16-bit parameters) ->
+Used by DGCBucket / DGCBatch at W > 1, through the ``Receiver`` both engines share: the
+back half of a step — packed payload -> allgather (``SingleExchange`` or ``SplitExchange``;
+for 16-bit parameters ``HalfExchange``, one allgather, or ``HalfSplitExchange``) ->
 zero_() or sparse re-zero -> scatter; ``parts="auto"`` splits a
 step of >= 2^21 gathered entries (2 parts at W <= 4, 4 at W = 8) and leaves smaller ones
 to one allgather: each extra collective costs ~35 us of fixed hand-off
 and hides at most its share of the scatter, which at 2M entries (flat-1B, W = 2: 0.07
 ms) only breaks even and at VGG-16-BN's 1.1M (W = 8) loses.
+
+16-bit parameters (bf16 / fp16) split only when asked — an integer ``exchange_parts`` or
+``DGC_EXCHANGE_PARTS``; ``"auto"`` alone keeps their one allgather, its thresholds being
+fp32 measurements. Their phases are K6-16 (``dgc_scatter_split16``): the same windows, each
+index written once with its rank-order sum, every add and the 1/W scale rounded to the
+dtype — ``dgc_decompress_packed16``'s result bit for bit (tests/test_gpu_split16.py) with
+no pass over the output but the zero fill, so nothing dense is left after the last part.
 
 ``DGC_EXCHANGE_PARTS`` overrides ``"auto"``; every rank must issue the same collectives,
 so an override is checked across the ranks when the layout is built (``agree``).
@@ -31,7 +38,8 @@ import torch
 
 from . import _lib, comm
 
-__all__ = ["HalfExchange", "Receiver", "ReceiveSide", "ReuseMemory", "SingleExchange", "SplitExchange", "split_parts"]
+__all__ = ["HalfExchange", "HalfSplitExchange", "Receiver", "ReceiveSide", "ReuseMemory", "SingleExchange",
+           "SplitExchange", "split_parts"]
 
 
 def split_parts(world, capacity, parts="auto"):
@@ -131,6 +139,11 @@ class SingleExchange(_Exchange):
             self._run("dgc_decompress_packed_over", [gathered, prev], handles, out, scale)
 
 
+def _dense_only16(what, dtype):
+    """The refusal of a scatter without its fill (dense=False) on 16-bit parameters."""
+    return NotImplementedError(f"{what}.decompress: dense=False on {dtype} parameters")
+
+
 class HalfExchange(_Exchange):
     """One allgather of the whole payload and the 16-bit packed decompress (bf16 / fp16
     parameters): zero_(), the runs in rank order (each add rounded to the dtype) and the
@@ -151,17 +164,19 @@ class HalfExchange(_Exchange):
             ctypes.c_void_p(self.status.decompress_words), _lib.stream_of(self.device)), "dgc_decompress_packed16")
 
     def scatter(self, gathered, handles, out, scale, cleared):
-        raise NotImplementedError(f"{self.status.what}.decompress: dense=False on {self.dtype} parameters")
+        raise _dense_only16(self.status.what, self.dtype)
 
     def clear(self, prev_gathered, out, stream):
         raise NotImplementedError(f"{self.status.what}: fill='sparse' on {self.dtype} parameters (the 16-bit "
                                   "decompress is the dense fill with the scatter)")
 
 
-class SplitExchange(_Exchange):
-    """The split payload of this rank, ``nbuf`` part-major gather buffers and the
-    phase scatter's workspace."""
+class _SplitLayout(_Exchange):
+    """What the split exchanges share: the split payload of this rank, ``nbuf`` part-major
+    gather buffers, the phase scatter's workspace (sized by ``workspace``, the name of
+    its C entry point) and ``send``."""
     streamed = True
+    workspace = "dgc_decompress_split_workspace"
 
     def __init__(self, capacity, numel, world, parts, vdtype, idtype, device, nbuf):
         L = self._L = _lib.lib()
@@ -176,9 +191,9 @@ class SplitExchange(_Exchange):
         self.split = torch.zeros(nb, dtype=torch.uint8, device=device)   # its scratch must start zero
         self.gathers = [torch.zeros(self.parts * self.world * self.part_bytes, dtype=torch.uint8, device=device)
                         for _ in range(nbuf)]
-        wsz = L.dgc_decompress_split_workspace(self.numel, self.world, self.parts, self.capacity)
+        wsz = getattr(L, self.workspace)(self.numel, self.world, self.parts, self.capacity)
         if wsz == 0:
-            raise ValueError(f"dgc_decompress_split_workspace: world {world}, parts {parts}")
+            raise ValueError(f"{self.workspace}: world {world}, parts {parts}")
         self.ws, self.device = torch.empty(wsz, dtype=torch.uint8, device=device), device
 
     def send(self, payload, gathered):
@@ -191,6 +206,10 @@ class SplitExchange(_Exchange):
         return [comm.allgather_packed_async(self.split[p * pb:(p + 1) * pb],
                                             out=gathered[p * W * pb:(p + 1) * W * pb])
                 for p in range(self.parts)]
+
+
+class SplitExchange(_SplitLayout):
+    """The split exchange of fp32 parameters: K6's phase scatter and the sparse re-zero."""
 
     def scatter(self, gathered, handles, out, scale, cleared):
         """The phases: each waits for its part (a stream wait under RCCL) and scatters
@@ -209,6 +228,34 @@ class SplitExchange(_Exchange):
         _lib.check(self._L.dgc_clear_split(prev_gathered.data_ptr(), self.world, self.parts, self.capacity, self.vd,
                                            self.id, out.data_ptr(), self.numel, self.ws.data_ptr(), self.ws.numel(),
                                            stream), "dgc_clear_split")
+
+
+class HalfSplitExchange(_SplitLayout):
+    """The split exchange of bf16 / fp16 parameters: ``dgc_fill_zero16``, then K6-16's phase
+    scatter (``dgc_scatter_split16``) — every index written once with its rank-order sum,
+    each add and the 1/W scale rounded to the dtype, ``HalfExchange``'s result bit for bit
+    with no pass over ``out`` but the fill. Always dense, as ``HalfExchange``: ``clear``
+    refuses with its message (``Receiver.scatter`` refuses dense=False)."""
+    workspace = "dgc_decompress_split16_workspace"
+    clear = HalfExchange.clear
+
+    def __init__(self, capacity, numel, world, parts, vdtype, idtype, dtype, device, status):
+        super().__init__(capacity, numel, world, parts, vdtype, idtype, device, 1)
+        self.dtype, self.status = dtype, status
+
+    def fill(self, out, stream):
+        """zero_() of the 16-bit ``out`` as one dense fill on ``stream``."""
+        _lib.check(self._L.dgc_fill_zero16(out.data_ptr(), self.numel, stream), "dgc_fill_zero16")
+
+    def scatter(self, gathered, handles, out, scale, cleared):
+        """The phases onto an ``out`` that holds +0: each waits for its part, then
+        scatters what has landed."""
+        L, st = self._L, _lib.stream_of(self.device)
+        for p, h in enumerate(handles):
+            h.wait()
+            _lib.check(L.dgc_scatter_split16(gathered.data_ptr(), self.world, self.parts, p, self.capacity, self.vd,
+                                             self.id, out.data_ptr(), _lib.VD[self.dtype], self.numel, scale,
+                                             self.ws.data_ptr(), self.ws.numel(), st), "dgc_scatter_split16")
 
 
 class ReuseMemory:
@@ -239,7 +286,9 @@ class Receiver(ReuseMemory):
     -> ``grad.zero_()`` (dgc/compression.py:191) -> the scatter of the gathered entries.
 
     ``dtype``: the parameters'. bf16 / fp16 take ``HalfExchange``: one part, always the
-    dense 16-bit decompress, no fp32 decompress workspace (``dec_ws`` is None).
+    dense 16-bit decompress, no fp32 decompress workspace (``dec_ws`` is None) — or, with
+    an explicit ``exchange_parts`` / ``DGC_EXCHANGE_PARTS`` above 1, ``HalfSplitExchange``
+    (``"auto"`` alone never splits them); dense too, ``fill`` stays ``"inline"``.
 
     ``fill``: how the zero_() is done. ``"inline"`` (``"auto"``, and always for 16-bit
     parameters) is a dense fill with the scatter. ``"sparse"`` (opt-in) treats ``out``
@@ -266,7 +315,11 @@ class Receiver(ReuseMemory):
         self.rank_stride, self.voff, self.ioff = _lib.payload_layout(self.capacity, vdtype, idtype)
         # (W = 1 exchanges too when comm.one_rank_collectives(): the RCCL tests' one-rank group)
         self.exchanging = self.world > 1 or comm.one_rank_collectives()
-        self.parts = 1 if half else split_parts(self.world, self.capacity, exchange_parts)
+        # 16-bit: "auto" alone never splits ("auto"'s thresholds are fp32 W > 1 measurements;
+        # the 16-bit scatter has none yet); an explicit count or DGC_EXCHANGE_PARTS does
+        asked = exchange_parts != "auto" or bool(os.environ.get("DGC_EXCHANGE_PARTS"))
+        self.parts = split_parts(self.world, self.capacity, exchange_parts) if asked or not half else 1
+        self.half, self.dtype, self.status = half, dtype, status
         # bytes appended to every rank's payload, after the packed entries (None when the
         # exchange is split, which carries the sparse entries only)
         self.extra_off = None
@@ -276,7 +329,9 @@ class Receiver(ReuseMemory):
         nbuf = 2 if self.fill == "sparse" else 1
         self.payloads = [torch.zeros(self.rank_stride, dtype=torch.uint8, device=device) for _ in range(nbuf)]
         if self.parts > 1:
-            self.xchg = SplitExchange(self.capacity, self.numel, self.world, self.parts, vdtype, idtype, device, nbuf)
+            self.xchg = (HalfSplitExchange(self.capacity, self.numel, self.world, self.parts, vdtype, idtype, dtype,
+                                           device, status) if half else
+                         SplitExchange(self.capacity, self.numel, self.world, self.parts, vdtype, idtype, device, nbuf))
             self.gathers = self.xchg.gathers
         else:
             self.gathers = ([torch.zeros(self.world * self.rank_stride, dtype=torch.uint8, device=device)
@@ -287,7 +342,7 @@ class Receiver(ReuseMemory):
         # what other files read: the split exchange or None, the fp32 single one's workspace or None
         self.split = self.xchg if self.parts > 1 else None
         self.dec_ws = None if half or self.parts > 1 else self.xchg.ws
-        if not half:   # (the 16-bit decompress writes status's words itself)
+        if not half or self.parts > 1:   # (the one-allgather 16-bit decompress writes status's words itself)
             status.bind(self.xchg.ws)
         self._par, self._inflight = 0, []
 
@@ -333,7 +388,10 @@ class Receiver(ReuseMemory):
             self.xchg.fill(out, stream)
 
     def scatter(self, out, cleared=False):
-        """Only the entries, onto an ``out`` that ``zero`` filled (``cleared``: re-zeroed)."""
+        """Only the entries, onto an ``out`` that ``zero`` filled (``cleared``: re-zeroed).
+        16-bit parameters refuse (``HalfExchange.scatter``), split or not."""
+        if self.half and self.parts > 1:
+            raise _dense_only16(self.status.what, self.dtype)
         cur = self.gathered
         self.xchg.scatter(cur, self._take(), out, self.scale, cleared)
         self.remember(out, cur)

@@ -431,6 +431,41 @@ int dgc_scatter_split(const void* gathered, int32_t world, int32_t parts, int32_
 int dgc_clear_split(const void* prev_gathered, int32_t world, int32_t parts, int64_t capacity, int32_t vdtype,
                     int32_t idtype, float* grad, int64_t n, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the split exchange onto a bf16 / fp16 gradient (dtype = DGC_BF16 / DGC_F16): K6-16 ----
+ * dgc_scatter_split's phases with the arithmetic of the reference's decompress run on a
+ * 16-bit tensor (dgc/compression.py:186-194): for every index i in the gathered runs,
+ *     a = +0;  for each entry (v, i) in run order (rank 0's first): a = rd(a + rd(widen(v)))
+ *     grad[i] = scale == 1 ? a : rd(a * scale)
+ * rd = round to nearest even to `dtype` — values.type(dtype) (:186-187), every add of
+ * index_put_(accumulate=True) (:191) and grad.mul_(1/W) (:193) rounded to the tensor's
+ * dtype — the sums of dgc_decompress_packed16, bit for bit. Every index is written once, by
+ * one 2-byte store; slots without an entry are not written, grad is never read and no
+ * atomics touch it. vdtype: DGC_F32, DGC_F16 or DGC_BF16 (dgc_payload_split copies all
+ * three). Called for part = 0, 1, ... in order on one workspace after part `part` landed:
+ * phase p writes exactly the indices below the minimum over ranks of part p's bound and not
+ * below part p-1's (cut at the index, where dgc_scatter_split stops at a super-chunk edge),
+ * the last phase the rest. grad holds +0 before part 0 (dgc_fill_zero16), which also resets
+ * the workspace's status words. Errors as dgc_scatter_split's: an index outside [0, n) is dropped (status bit 0,
+ * sink[0]; a negative index is not wrapped), a part header's count outside
+ * [0, part_capacity] is clamped (bit 2, sink[1]), a run out of order is regrouped (bit 1);
+ * dgc_decompress_status and dgc_decompress_bind_sink take its workspace.
+ * DGC_ERR_INVALID / DGC_ERR_DTYPE / DGC_ERR_WORKSPACE before anything is launched for a
+ * null gathered or grad, parts outside 2..8, world * parts > 64, part outside 0..parts-1, a
+ * dtype outside the above, an odd grad address, or a null, unaligned or too small workspace
+ * (the status dgc_scatter_split gives each). */
+/* The phase scatter's workspace (dgc/compression.py:179-194 needs none; the bounds, the
+ * overflow queue and the regroup area of dgc_decompress_split_workspace, whose 12 B per
+ * regrouped entry cover 2-byte values): the same size; 0 for world * parts > 64. */
+size_t dgc_decompress_split16_workspace(int64_t n, int32_t world, int32_t parts, int64_t capacity);
+/* One phase of dgc/compression.py:186-194 on a 16-bit gradient (above). */
+int dgc_scatter_split16(const void* gathered, int32_t world, int32_t parts, int32_t part, int64_t capacity,
+                        int32_t vdtype, int32_t idtype, void* grad, int32_t dtype, int64_t n, float scale, void* ws,
+                        size_t ws_bytes, void* stream);
+/* grad.zero_() (dgc/compression.py:191) of a 16-bit tensor: +0 bits over grad[0..n) with
+ * one-shot 16-B stores, 2-byte stores for the up to 7 elements before the first and after
+ * the last 16-B boundary (a 2-byte-aligned buffer: any view of a 16-bit tensor). */
+int dgc_fill_zero16(void* grad, int64_t n, void* stream);
+
 /* Status word written by the decompress kernels: bit 0 = an index was out of
  * range [0, n) and was ignored (the reference's index_put_ raises,
  * dgc/compression.py:191); bit 1 = a run was not non-decreasing; bit 2 = a packed
