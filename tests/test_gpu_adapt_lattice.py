@@ -10,7 +10,7 @@ served, where the landed count came from, what the spilled segments did — stan
 ``PAIRS`` as data: a rewrite that changes the routing has to edit it. ``staircase.route``
 restates csrc/select.hip's routing and tests/test_staircase_cpu.py holds the table to it.
 
-Not pinned here: N > 2^32, the sample window (S > 32768), clipping, W > 1.
+Not pinned here: N > 2^32, clipping, W > 1 (the sample window, S > 32768: test_gpu_k3_edges.py).
 """
 import ctypes
 import functools
