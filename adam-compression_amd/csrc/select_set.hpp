@@ -14,9 +14,11 @@ namespace dgc {
 // across the k boundary (#keys >= kth == k) every top-k is that set, whatever order
 // and tie rule produced it, so it is emitted in index order and the exact replay (K5)
 // skips the tensor (rs_nth = 3). Tied, the replay runs as always. The k-th largest is
-// found by a radix select over key - key(t_cur) (every candidate is >= t_cur) in three
-// 11-bit passes over the open range up to 0x7FFFFFFF; the emit carries the wire casts
-// and the masking of the K5 emit.
+// found by a radix select over key - key(t_cur) (every candidate is >= t_cur) in two
+// passes over the kSetSpan = 25 bits above key(t_cur): kSetBins0 = 4096 bins of bits
+// 13-24, clamped (the top bin also takes every key past the span; the k-th largest
+// there goes to the replay), then kSetBins1 = 8192 bins of bits 0-12 under the first
+// pass's prefix; the emit carries the wire casts and the masking of the K5 emit.
 //
 // Over G co-resident workgroups of ONE launch (the tensor's BT_SET workgroups: kSetGDefault,
 // up to kSetGBig for a capacity past kSetGDefault x kSetCoopMin — VGG-16-BN's fc6, where four
@@ -25,7 +27,7 @@ namespace dgc {
 // ~10 us to dispatch): a set of more than kSetCoopMin candidates is cut into G contiguous
 // stretches of rounds, each workgroup's keys in its registers; the radix passes'
 // histograms and the per-stretch counts go through device atomics with a barrier
-// between the phases (pass 1 | pass 2 | pass 3 | counts), and each
+// between the phases (pass 0 | pass 1 | counts), and each
 // workgroup emits its stretch's selected entries at the count of the stretches before
 // it plus their order inside it — the index order, as one workgroup emits it. A set of
 // up to kSetRegC x 1024 candidates takes the same code on one workgroup, with no

@@ -221,7 +221,12 @@ int dgc_kth_largest(const float* x, int64_t n, int64_t k, float* thr_out,
  * vec (length numel) is read; with params.update_memory its emitted slots are
  * zeroed, and mmt's too when params.masking (dgc_compress forces update_memory=1). thr0 is the device scalar from dgc_kth_largest. Writes
  * values_out[0..n), indices_out[0..n) (ascending), *count_out = n (device int64)
- * and *info_out (device, may be NULL). */
+ * and *info_out (device, may be NULL).
+ * Workspace: with params.resample_order = 0 its contents on entry do not matter. With
+ * resample_order = 1 zero-fill it before the first call on it (later calls may reuse
+ * it as they left it): the index-order set path merges its radix histograms into
+ * workspace words that are zero at rest — each call re-zeroes what it used — and reads
+ * the previous call's broken-barrier flag there. */
 size_t dgc_select_workspace(int64_t numel, int64_t num_selects);
 int dgc_select(float* vec, float* mmt, const float* thr0, const dgc_select_params* params,
                void* values_out, void* indices_out, int64_t* count_out,

@@ -276,11 +276,12 @@ def biased_sample_gradient(n, stride, start):
 
 
 def test_batch_index_order_biased_samples():
-    """K5s bounds its radix passes from 4096 samples taken at fixed candidate positions
-    (rounds 0, 4, 8, 12 in index order) once a set passes 16384 candidates. Here those
-    positions hold the set's largest keys (``biased_sample_gradient``), so the sampled
-    bound sits above the k-th key and the count check must drop it: the set (a resample
-    over ~70k candidates, k = 10000, untied) still equals torch's top-k."""
+    """K5s bounds its radix passes from below by key(t_cur) — every candidate is >= t_cur —
+    whatever order the candidates come in (an earlier K5s sampled a bound at fixed
+    candidate positions, rounds 0, 4, 8, 12 in index order; this gradient was built
+    against it). Here those positions hold the set's largest keys
+    (``biased_sample_gradient``): the set (a resample over ~70k candidates, k = 10000,
+    untied, on more than one workgroup) still equals torch's top-k."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     import random

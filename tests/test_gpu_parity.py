@@ -155,7 +155,10 @@ def test_kth_largest_specials(L):
 
 # ----------------------------------------------------------------------------- K4
 def select_dev(L, vec_np, mmt_np, thr, attrs, *, upper=1.3, lower=0.8, max_iters=10, resample=True,
-               masking=True, fp16=False, int32=False, update_memory=True, sync=1):
+               masking=True, fp16=False, int32=False, update_memory=True, sync=1, resample_order=0, ws=None):
+    """``resample_order=1`` (an untied resample's set in index order, K5s) needs ``ws``: a
+    zero-filled workspace of dgc_select_workspace(numel, k) bytes, which may be passed again
+    as the call before left it (include/dgc_hip.h)."""
     from dgc import _lib
     numel, k, S, ks, stride = attrs
     p = _lib.SelectParams()
@@ -164,6 +167,7 @@ def select_dev(L, vec_np, mmt_np, thr, attrs, *, upper=1.3, lower=0.8, max_iters
     p.upper, p.lower = upper, lower
     p.max_iters, p.resample, p.masking = max_iters, int(resample), int(masking)
     p.vdtype, p.idtype, p.update_memory = int(fp16), int(int32), int(update_memory)
+    p.resample_order = int(resample_order)
     tv, tm = to_dev(vec_np), to_dev(mmt_np)
     t0 = torch.tensor([thr], dtype=torch.float32, device=DEV)
     vals = torch.empty(k, dtype=torch.float16 if fp16 else torch.float32, device=DEV)
@@ -171,7 +175,10 @@ def select_dev(L, vec_np, mmt_np, thr, attrs, *, upper=1.3, lower=0.8, max_iters
     cnt = torch.zeros(1, dtype=torch.int64, device=DEV)
     info = torch.zeros(_lib.INFO_BYTES, dtype=torch.uint8, device=DEV)
     wsz = L.dgc_select_workspace(numel, k)
-    ws = torch.empty(wsz, dtype=torch.uint8, device=DEV)
+    assert resample_order == 0 or ws is not None, "resample_order=1: pass a zero-filled workspace"
+    if ws is None:
+        ws = torch.empty(wsz, dtype=torch.uint8, device=DEV)
+    assert ws.numel() == wsz and ws.dtype == torch.uint8
     check(L, L.dgc_select(P(tv), P(tm), P(t0), ctypes.byref(p), P(vals), P(idx), P(cnt), P(info), P(ws), wsz,
                           sync, stream()))
     torch.cuda.synchronize()
