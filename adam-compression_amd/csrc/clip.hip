@@ -15,7 +15,8 @@
 #include <algorithm>
 #include <cmath>
 
-#include "dgc_common.hpp"
+#include "dispatch.hpp"
+#include "payload.hpp"
 
 namespace dgc {
 
@@ -34,16 +35,6 @@ struct ClipChunkT {
 };
 using ClipChunk = ClipChunkT<float>;
 using ClipChunk16 = ClipChunkT<const uint16_t>;   // K0-16: bf16 / fp16 sources
-
-template <typename C>
-__device__ __forceinline__ int chunk_tensor(const C& c, int b) {
-    int lo = 0, hi = c.count - 1;        // bstart[t] <= b < bstart[t + 1]
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (c.bstart[mid] <= b) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ float nan_max(float a, float b) { return a != a ? a : (b != b ? b : fmaxf(a, b)); }
 
@@ -69,7 +60,7 @@ __device__ __forceinline__ double block_fold(double x) {
 template <bool MAX, bool ROUND16>
 __global__ void __launch_bounds__(kBlock) k_stat_partial(ClipChunk c, double* __restrict__ part) {
     const int b = (int)blockIdx.x;
-    const int t = chunk_tensor(c, b);
+    const int t = chunk_of(c, b);
     const float* __restrict__ src = c.src[t];
     const int64_t n = c.n[t];
     const int64_t j = b - c.bstart[t];
@@ -112,7 +103,7 @@ typedef uint32_t u2v __attribute__((ext_vector_type(2)));
 template <int DT, bool MAX>
 __global__ void __launch_bounds__(kBlock) k_stat_partial16(ClipChunk16 c, double* __restrict__ part) {
     const int b = (int)blockIdx.x;
-    const int t = chunk_tensor(c, b);
+    const int t = chunk_of(c, b);
     DGC_GLB const uint16_t* src = glb(c.src[t]);
     const int64_t n = c.n[t];
     const int64_t j = b - c.bstart[t];
@@ -243,18 +234,13 @@ int grad_stats(const float* const* srcs, const int64_t* numels, int32_t count, i
         const dim3 bd(kBlock);
         if (blocks > 0) {
             const dim3 gd((unsigned)blocks);
-            if (mx) {
-                if (r16) hipLaunchKernelGGL((k_stat_partial<true, true>), gd, bd, 0, st, c, part);
-                else hipLaunchKernelGGL((k_stat_partial<true, false>), gd, bd, 0, st, c, part);
-            } else {
-                if (r16) hipLaunchKernelGGL((k_stat_partial<false, true>), gd, bd, 0, st, c, part);
-                else hipLaunchKernelGGL((k_stat_partial<false, false>), gd, bd, 0, st, c, part);
-            }
+            with_bool(mx, [&](auto MAX) { with_bool(r16, [&](auto R16) {
+                hipLaunchKernelGGL((k_stat_partial<MAX(), R16()>), gd, bd, 0, st, c, part); }); });
             DGC_LAUNCHED();
         }
         const dim3 gf((unsigned)c.count);
-        if (mx) hipLaunchKernelGGL((k_stat_final<true>), gf, bd, 0, st, c, part, stats, 0);
-        else hipLaunchKernelGGL((k_stat_final<false>), gf, bd, 0, st, c, part, stats, kind == DGC_STAT_NORM2 ? 1 : 0);
+        with_bool(mx, [&](auto MAX) {
+            hipLaunchKernelGGL((k_stat_final<MAX()>), gf, bd, 0, st, c, part, stats, kind == DGC_STAT_NORM2 ? 1 : 0); });
         DGC_LAUNCHED();
     }
     return DGC_OK;
@@ -287,18 +273,6 @@ int clip_coefs(const float* stats, int32_t count, int32_t mode, float max_norm, 
 
 // K0-16: the statistic of bf16 / fp16 tensors, as torch leaves it in a 0-dim tensor of the
 // dtype (x.norm(2), x.abs().max()): the fp64 result rounded to fp32, then to the dtype.
-template <int DT>
-static void launch_stats16(bool mx, const ClipChunk16& c, int64_t blocks, double* part, float* stats, hipStream_t st) {
-    const dim3 bd(kBlock), gf((unsigned)c.count);
-    if (blocks > 0) {
-        const dim3 gd((unsigned)blocks);
-        if (mx) hipLaunchKernelGGL((k_stat_partial16<DT, true>), gd, bd, 0, st, c, part);
-        else hipLaunchKernelGGL((k_stat_partial16<DT, false>), gd, bd, 0, st, c, part);
-    }
-    if (mx) hipLaunchKernelGGL((k_stat_final<true, DT, ClipChunk16>), gf, bd, 0, st, c, part, stats, 0);
-    else hipLaunchKernelGGL((k_stat_final<false, DT, ClipChunk16>), gf, bd, 0, st, c, part, stats, 1);   // the 2-norm
-}
-
 int grad_stats16(const void* const* srcs, const int64_t* numels, int32_t count, int32_t kind, int32_t dtype,
                  float* stats, void* ws, size_t ws_bytes, hipStream_t st) {
     if (count < 0 || (count > 0 && (!srcs || !numels || !stats)))
@@ -306,7 +280,7 @@ int grad_stats16(const void* const* srcs, const int64_t* numels, int32_t count, 
     if (kind == DGC_STAT_SUMSQ)
         DGC_FAIL(DGC_ERR_INVALID, "dgc_grad_stats16: DGC_STAT_SUMSQ (the global variants) is not taken on 16-bit tensors");
     if (kind != DGC_STAT_NORM2 && kind != DGC_STAT_ABSMAX) DGC_FAIL(DGC_ERR_INVALID, "dgc_grad_stats16: kind %d", (int)kind);
-    if (dtype != DGC_BF16 && dtype != DGC_F16)
+    if (!is16(dtype))
         DGC_FAIL(DGC_ERR_DTYPE, "dgc_grad_stats16: dtype must be DGC_BF16 or DGC_F16 (got %d)", (int)dtype);
     if (count == 0) return DGC_OK;
     if (stat_partials(numels, count) < 0) DGC_FAIL(DGC_ERR_INVALID, "dgc_grad_stats16: negative numel");
@@ -331,9 +305,11 @@ int grad_stats16(const void* const* srcs, const int64_t* numels, int32_t count, 
             c.poff[i] = poff;
             poff += ceil_div(c.n[i], (int64_t)kStatChunk);
         }
-        const bool mx = kind == DGC_STAT_ABSMAX;
-        if (dtype == DGC_BF16) launch_stats16<DGC_BF16>(mx, c, blocks, part, stats, st);
-        else launch_stats16<DGC_F16>(mx, c, blocks, part, stats, st);
+        const dim3 bd(kBlock), gd((unsigned)blocks), gf((unsigned)c.count);
+        with_h16(dtype, [&](auto DT) { with_bool(kind == DGC_STAT_ABSMAX, [&](auto MAX) {
+            if (blocks > 0) hipLaunchKernelGGL((k_stat_partial16<DT(), MAX()>), gd, bd, 0, st, c, part);
+            // the final's last argument: the root of the sum of squares (the 2-norm)
+            hipLaunchKernelGGL((k_stat_final<MAX(), DT(), ClipChunk16>), gf, bd, 0, st, c, part, stats, MAX() ? 0 : 1); }); });
         DGC_LAUNCHED();
     }
     return DGC_OK;
@@ -353,12 +329,11 @@ k_clip_coefs16(const float* stats, int32_t count, float max_norm, float* clip) {
 
 int clip_coefs16(const float* stats, int32_t count, float max_norm, int32_t dtype, float* clip, hipStream_t st) {
     if (count < 0 || (count > 0 && (!stats || !clip))) DGC_FAIL(DGC_ERR_INVALID, "dgc_clip_coefs16: null argument");
-    if (dtype != DGC_BF16 && dtype != DGC_F16)
+    if (!is16(dtype))
         DGC_FAIL(DGC_ERR_DTYPE, "dgc_clip_coefs16: dtype must be DGC_BF16 or DGC_F16 (got %d)", (int)dtype);
     if (count == 0) return DGC_OK;
     const dim3 gd((unsigned)ceil_div(count, kBlock)), bd(kBlock);
-    if (dtype == DGC_BF16) hipLaunchKernelGGL(k_clip_coefs16<DGC_BF16>, gd, bd, 0, st, stats, count, max_norm, clip);
-    else hipLaunchKernelGGL(k_clip_coefs16<DGC_F16>, gd, bd, 0, st, stats, count, max_norm, clip);
+    with_h16(dtype, [&](auto DT) { hipLaunchKernelGGL(k_clip_coefs16<DT()>, gd, bd, 0, st, stats, count, max_norm, clip); });
     DGC_LAUNCHED();
     return DGC_OK;
 }
@@ -366,7 +341,7 @@ int clip_coefs16(const float* stats, int32_t count, float max_norm, int32_t dtyp
 template <int CLIP>
 __global__ void __launch_bounds__(kBlock) k_clip_apply(ClipChunk c, ClipArg ca) {
     const int b = (int)blockIdx.x;
-    const int t = chunk_tensor(c, b);
+    const int t = chunk_of(c, b);
     float* __restrict__ x = c.src[t];
     const int64_t n = c.n[t];
     const float cf = clip_coef<CLIP>(ca, c.first + t);
@@ -391,8 +366,7 @@ int clip_apply(float* const* tensors, const int64_t* numels, int32_t count, int3
         if (blocks == 0) continue;
         const dim3 gd((unsigned)blocks), bd(kBlock);
         const ClipArg ca{clip, value};
-        if (kind == DGC_CLIP_SCALE) hipLaunchKernelGGL((k_clip_apply<DGC_CLIP_SCALE>), gd, bd, 0, st, c, ca);
-        else hipLaunchKernelGGL((k_clip_apply<DGC_CLIP_CLAMP>), gd, bd, 0, st, c, ca);
+        with_clip_on(kind, [&](auto CLIP) { hipLaunchKernelGGL((k_clip_apply<CLIP()>), gd, bd, 0, st, c, ca); });
         DGC_LAUNCHED();
     }
     return DGC_OK;

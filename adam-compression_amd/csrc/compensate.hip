@@ -18,7 +18,8 @@
 // ~1/3 of its lines).
 #include <algorithm>
 
-#include "dgc_common.hpp"
+#include "dispatch.hpp"
+#include "payload.hpp"
 
 namespace dgc {
 
@@ -148,24 +149,18 @@ static int launch_comp(const float* g, float* m, float* v, float* o, int64_t n, 
             auto m4 = reinterpret_cast<float4*>(m);
             auto v4 = reinterpret_cast<float4*>(v);
             auto o4 = reinterpret_cast<float4*>(o);
-            if (sample)
-                hipLaunchKernelGGL((k_compensate4<NEST, ACC, true, CLIP>), dim3((unsigned)grid), dim3(kBlock), 0, st,
-                                   g4, m4, v4, o4, n4, mom, sp, (int)write_through(n), ca);
-            else
-                hipLaunchKernelGGL((k_compensate4<NEST, ACC, false, CLIP>), dim3((unsigned)grid), dim3(kBlock), 0, st,
-                                   g4, m4, v4, o4, n4, mom, sp, (int)write_through(n), ca);
+            with_bool(sample, [&](auto SAMPLE) {
+                hipLaunchKernelGGL((k_compensate4<NEST, ACC, SAMPLE(), CLIP>), dim3((unsigned)grid), dim3(kBlock), 0, st,
+                                   g4, m4, v4, o4, n4, mom, sp, (int)write_through(n), ca); });
             DGC_LAUNCHED();
         }
         done = n4 * 4;
     }
     if (done < n) {
         const int grid = grid_for(n - done);
-        if (sample)
-            hipLaunchKernelGGL((k_compensate1<NEST, ACC, true, CLIP>), dim3(grid), dim3(kBlock), 0, st,
-                               g, m, v, o, done, n, mom, sp, ca);
-        else
-            hipLaunchKernelGGL((k_compensate1<NEST, ACC, false, CLIP>), dim3(grid), dim3(kBlock), 0, st,
-                               g, m, v, o, done, n, mom, sp, ca);
+        with_bool(sample, [&](auto SAMPLE) {
+            hipLaunchKernelGGL((k_compensate1<NEST, ACC, SAMPLE(), CLIP>), dim3(grid), dim3(kBlock), 0, st,
+                               g, m, v, o, done, n, mom, sp, ca); });
         DGC_LAUNCHED();
     }
     return DGC_OK;
@@ -297,44 +292,23 @@ static int mt_chunk(const float* const* srcs, const int64_t* numels, const int64
     return DGC_OK;
 }
 
-// The clip kinds of a K1 call: SCALE needs the coefficient table, CLAMP a table or a value.
-static int clip_check(int32_t kind, const float* clip, const char* who) {
-    if (!clip_kind_ok(kind)) DGC_FAIL(DGC_ERR_INVALID, "%s: clip kind %d", who, (int)kind);
-    if (kind == DGC_CLIP_SCALE && !clip) DGC_FAIL(DGC_ERR_INVALID, "%s: DGC_CLIP_SCALE needs the coefficient table", who);
-    return DGC_OK;
-}
-
-template <bool NEST, bool ROUND16>
-static void launch_mt(int32_t kind, dim3 gd, dim3 bd, hipStream_t st, const MtChunk& c, float* mmt, float* out,
-                      float mom, ClipArg ca, int t0) {
-    if (kind == DGC_CLIP_SCALE)
-        hipLaunchKernelGGL((k_compensate_mt<NEST, ROUND16, DGC_CLIP_SCALE>), gd, bd, 0, st, c, mmt, out, mom, ca, t0);
-    else if (kind == DGC_CLIP_CLAMP)
-        hipLaunchKernelGGL((k_compensate_mt<NEST, ROUND16, DGC_CLIP_CLAMP>), gd, bd, 0, st, c, mmt, out, mom, ca, t0);
-    else
-        hipLaunchKernelGGL((k_compensate_mt<NEST, ROUND16, DGC_CLIP_NONE>), gd, bd, 0, st, c, mmt, out, mom, ca, t0);
-}
-
 int compensate_multi(const float* const* srcs, const int64_t* numels, const int64_t* offsets, int32_t count,
                      int32_t round_to, float* mmt, float* out, float mom, bool nesterov, int32_t clip_kind,
                      ClipArg ca, hipStream_t st) {
     if (count < 0 || (count > 0 && (!srcs || !numels || !offsets || !mmt || !out)))
         DGC_FAIL(DGC_ERR_INVALID, "dgc_compensate_multi: null argument");
     if (round_to != DGC_F32 && round_to != DGC_F16) DGC_FAIL(DGC_ERR_DTYPE, "dgc_compensate_multi: round_to");
-    DGC_TRY(clip_check(clip_kind, ca.tab, "dgc_compensate_multi"));
+    DGC_TRY(check_clip("dgc_compensate_multi", clip_kind, ca.tab));
     for (int32_t t0 = 0; t0 < count; t0 += kMtMax) {
         MtChunk c;
         int64_t blocks;
         DGC_TRY(mt_chunk(srcs, numels, offsets, t0, count, c, blocks, "dgc_compensate_multi"));
         if (blocks == 0) continue;
         const dim3 gd((unsigned)blocks), bd(kBlock);
-        if (nesterov) {
-            if (round_to == DGC_F16) launch_mt<true, true>(clip_kind, gd, bd, st, c, mmt, out, mom, ca, t0);
-            else launch_mt<true, false>(clip_kind, gd, bd, st, c, mmt, out, mom, ca, t0);
-        } else {
-            if (round_to == DGC_F16) launch_mt<false, true>(clip_kind, gd, bd, st, c, mmt, out, mom, ca, t0);
-            else launch_mt<false, false>(clip_kind, gd, bd, st, c, mmt, out, mom, ca, t0);
-        }
+        with_bool(nesterov, [&](auto NEST) { with_bool(round_to == DGC_F16, [&](auto ROUND16) {
+            with_clip(clip_kind, [&](auto CLIP) {
+                hipLaunchKernelGGL((k_compensate_mt<NEST(), ROUND16(), CLIP()>), gd, bd, 0, st, c, mmt, out, mom, ca, t0);
+            }); }); });
         DGC_LAUNCHED();
     }
     return DGC_OK;
@@ -344,7 +318,7 @@ int gather_cast(const float* const* srcs, const int64_t* numels, const int64_t* 
                 int32_t dtype, hipStream_t st) {
     if (count < 0 || (count > 0 && (!srcs || !numels || !offsets || !dst)))
         DGC_FAIL(DGC_ERR_INVALID, "dgc_gather_cast: null argument");
-    if (dtype != DGC_F32 && dtype != DGC_F16 && dtype != DGC_BF16) DGC_FAIL(DGC_ERR_DTYPE, "dgc_gather_cast: dtype");
+    if (!float_dtype_ok(dtype)) DGC_FAIL(DGC_ERR_DTYPE, "dgc_gather_cast: dtype");
     for (int32_t t0 = 0; t0 < count; t0 += kMtMax) {
         MtChunk c;
         int64_t blocks;
@@ -372,13 +346,8 @@ int compensate_wire(const void* src, int32_t src_dtype, int32_t round_to, float*
     if (grid > 0x7FFFFFFFLL) DGC_FAIL(DGC_ERR_INVALID, "dgc_compensate_wire: n too large");
     const dim3 gd((unsigned)grid), bd(kBlock);
     const float div = (float)divisor;
-#define DGC_WIRE(NE, M) hipLaunchKernelGGL((k_compensate_wire<NE, M>), gd, bd, 0, st, src, mmt, out, n, mom, div)
-    if (nesterov) {
-        if (mode == 0) DGC_WIRE(true, 0); else if (mode == 1) DGC_WIRE(true, 1); else DGC_WIRE(true, 2);
-    } else {
-        if (mode == 0) DGC_WIRE(false, 0); else if (mode == 1) DGC_WIRE(false, 1); else DGC_WIRE(false, 2);
-    }
-#undef DGC_WIRE
+    with_bool(nesterov, [&](auto NEST) { with_mode<3>(mode, [&](auto MODE) {
+        hipLaunchKernelGGL((k_compensate_wire<NEST(), MODE()>), gd, bd, 0, st, src, mmt, out, n, mom, div); }); });
     DGC_LAUNCHED();
     return DGC_OK;
 }
@@ -462,8 +431,8 @@ static int check_ranks(const void* src, int32_t dtype, int32_t world, int64_t ra
                        const char* who) {
     if (n < 0 || (n > 0 && !src) || world < 1 || world > 4096)
         DGC_FAIL(DGC_ERR_INVALID, "%s: bad arguments (n %lld, world %d)", who, (long long)n, (int)world);
-    if (dtype != DGC_F32 && dtype != DGC_F16 && dtype != DGC_BF16) DGC_FAIL(DGC_ERR_DTYPE, "%s: wire dtype", who);
-    const int64_t es = dtype == DGC_F32 ? 4 : 2;
+    if (!wire_ok(dtype, true)) DGC_FAIL(DGC_ERR_DTYPE, "%s: wire dtype", who);
+    const int64_t es = vbytes(dtype);
     if (world > 1 && rank_stride < n * es)
         DGC_FAIL(DGC_ERR_INVALID, "%s: rank_stride %lld < %lld bytes of values", who, (long long)rank_stride,
                  (long long)(n * es));
@@ -480,9 +449,8 @@ int rank_sum(const void* src, int32_t dtype, int32_t world, int64_t rank_stride,
     if (n == 0) return DGC_OK;
     const dim3 gd((unsigned)ceil_div(n, (int64_t)kBlock * 4)), bd(kBlock);
     const char* s = static_cast<const char*>(src);
-    if (dtype == DGC_F32) hipLaunchKernelGGL((k_rank_sum<DGC_F32>), gd, bd, 0, st, s, rank_stride, world, n, average, dst);
-    else if (dtype == DGC_F16) hipLaunchKernelGGL((k_rank_sum<DGC_F16>), gd, bd, 0, st, s, rank_stride, world, n, average, dst);
-    else hipLaunchKernelGGL((k_rank_sum<DGC_BF16>), gd, bd, 0, st, s, rank_stride, world, n, average, dst);
+    with_wire16(dtype, [&](auto DT) {
+        hipLaunchKernelGGL((k_rank_sum<DT()>), gd, bd, 0, st, s, rank_stride, world, n, average, dst); });
     DGC_LAUNCHED();
     return DGC_OK;
 }
@@ -495,24 +463,10 @@ int compensate_ranks(const void* src, int32_t dtype, int32_t world, int64_t rank
     if (n == 0) return DGC_OK;
     const dim3 gd((unsigned)ceil_div(n, (int64_t)kBlock * 4)), bd(kBlock);
     const char* s = static_cast<const char*>(src);
-#define DGC_RANKS(NE, DT) \
-    hipLaunchKernelGGL((k_compensate_ranks<NE, DT>), gd, bd, 0, st, s, rank_stride, world, mmt, out, n, mom)
-    if (nesterov) {
-        if (dtype == DGC_F32) DGC_RANKS(true, DGC_F32); else DGC_RANKS(true, DGC_F16);
-    } else {
-        if (dtype == DGC_F32) DGC_RANKS(false, DGC_F32); else DGC_RANKS(false, DGC_F16);
-    }
-#undef DGC_RANKS
+    with_bool(nesterov, [&](auto NEST) { with_vd(dtype, [&](auto DT) {   // bf16 was refused above
+        hipLaunchKernelGGL((k_compensate_ranks<NEST(), DT()>), gd, bd, 0, st, s, rank_stride, world, mmt, out, n, mom); }); });
     DGC_LAUNCHED();
     return DGC_OK;
-}
-
-template <bool NEST, bool ACC>
-static int launch_comp_kind(int32_t kind, const float* g, float* m, float* v, float* o, int64_t n, float mom,
-                            SampleSpec sp, ClipArg ca, hipStream_t st) {
-    if (kind == DGC_CLIP_SCALE) return launch_comp<NEST, ACC, DGC_CLIP_SCALE>(g, m, v, o, n, mom, sp, ca, st);
-    if (kind == DGC_CLIP_CLAMP) return launch_comp<NEST, ACC, DGC_CLIP_CLAMP>(g, m, v, o, n, mom, sp, ca, st);
-    return launch_comp<NEST, ACC, DGC_CLIP_NONE>(g, m, v, o, n, mom, sp, ca, st);
 }
 
 // K1 with the gradient clipped as it is loaded (ca.tab points at this tensor's coefficient).
@@ -520,7 +474,7 @@ int compensate_clip(const float* grad, float* mmt, float* vec, float* out, int64
                     bool nesterov, bool accumulate, float* samples, int64_t s_start, int64_t s_stride,
                     int64_t s_count, int32_t clip_kind, ClipArg ca, hipStream_t st) {
     if (n < 0) DGC_FAIL(DGC_ERR_INVALID, "dgc_compensate: n < 0");
-    DGC_TRY(clip_check(clip_kind, ca.tab, "dgc_compensate"));
+    DGC_TRY(check_clip("dgc_compensate", clip_kind, ca.tab));
     if (n == 0) return DGC_OK;
     if (!grad || !mmt) DGC_FAIL(DGC_ERR_INVALID, "dgc_compensate: null grad/mmt");
     if (accumulate && !vec) DGC_FAIL(DGC_ERR_INVALID, "dgc_compensate: accumulate needs vec");
@@ -546,11 +500,9 @@ int compensate_clip(const float* grad, float* mmt, float* vec, float* out, int64
             return DGC_OK;
         }
     }
-    if (nesterov)
-        return accumulate ? launch_comp_kind<true, true>(clip_kind, grad, mmt, vec, out, n, momentum, sp, ca, st)
-                          : launch_comp_kind<true, false>(clip_kind, grad, mmt, vec, out, n, momentum, sp, ca, st);
-    return accumulate ? launch_comp_kind<false, true>(clip_kind, grad, mmt, vec, out, n, momentum, sp, ca, st)
-                      : launch_comp_kind<false, false>(clip_kind, grad, mmt, vec, out, n, momentum, sp, ca, st);
+    return with_bool(nesterov, [&](auto NEST) { return with_bool(accumulate, [&](auto ACC) {
+        return with_clip(clip_kind, [&](auto CLIP) {
+            return launch_comp<NEST(), ACC(), CLIP()>(grad, mmt, vec, out, n, momentum, sp, ca, st); }); }); });
 }
 
 int compensate(const float* grad, float* mmt, float* vec, float* out, int64_t n, float momentum,
@@ -681,16 +633,14 @@ extern "C" int dgc_mask_indices(float* mmt, float* vec, int64_t n, const void* i
                                 int64_t count, int32_t* bad_flag, void* stream) {
     if (!vec || (count > 0 && !indices) || !bad_flag)
         DGC_FAIL(DGC_ERR_INVALID, "dgc_mask_indices: null argument");
-    if (idtype != DGC_I64 && idtype != DGC_I32) DGC_FAIL(DGC_ERR_DTYPE, "dgc_mask_indices: index dtype");
+    if (!dgc::index_ok(idtype)) DGC_FAIL(DGC_ERR_DTYPE, "dgc_mask_indices: index dtype");
     if (count <= 0) return DGC_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int grid = dgc::grid_for(count);
-    if (idtype == DGC_I32)
-        hipLaunchKernelGGL(dgc::k_mask<int32_t>, dim3(grid), dim3(dgc::kBlock), 0, s, mmt, vec,
-                           static_cast<const int32_t*>(indices), count, n, bad_flag);
-    else
-        hipLaunchKernelGGL(dgc::k_mask<int64_t>, dim3(grid), dim3(dgc::kBlock), 0, s, mmt, vec,
-                           static_cast<const int64_t*>(indices), count, n, bad_flag);
+    dgc::with_id(idtype, [&](auto ID) {
+        using I = dgc::idx_t<decltype(ID)>;
+        hipLaunchKernelGGL(dgc::k_mask<I>, dim3(grid), dim3(dgc::kBlock), 0, s, mmt, vec, static_cast<const I*>(indices),
+                           count, n, bad_flag); });
     DGC_LAUNCHED();
     return DGC_OK;
 }

@@ -24,7 +24,8 @@
 // bf16 / fp16 gradient for the split exchange of 16-bit parameters — the kernels take the
 // output as a template parameter (Out<OD>): a rounding to the dtype after every add and
 // after the scale, one 2-byte store per index, 2 B/elem of fill.
-#include "dgc_common.hpp"
+#include "dispatch.hpp"
+#include "payload.hpp"
 
 #include <mutex>
 #include <utility>
@@ -101,13 +102,6 @@ __device__ __forceinline__ void flag_count(const DecWS& w) {
     raise_flag(w.sink ? w.sink + 1 : nullptr);
 }
 
-template <int VD>
-__device__ __forceinline__ float load_val(const void* p, long long e) {
-    if (VD == DGC_F16) return (float)((const DGC_GLB _Float16*)p)[e];   // typed: global_ loads; exact widening
-    if (VD == DGC_BF16) return bf16_to_f32(((const DGC_GLB uint16_t*)p)[e]);   // (K6-16's wire only)
-    return ((const DGC_GLB float*)p)[e];
-}
-
 // What the scatter writes. K6 (OD = DGC_F32): fp32 words, every add and the scale rounded
 // to fp32 by the instruction itself. K6-16 (OD = DGC_BF16 / DGC_F16, the split exchange of
 // 16-bit parameters): 2-byte elements, and rd() after every op — values.type(dtype), each
@@ -129,12 +123,6 @@ struct Out<DGC_F32> {
     static __device__ __forceinline__ float rd(float x) { return x; }
     static __device__ __forceinline__ T pack(float x) { return x; }
 };
-
-template <int ID>
-__device__ __forceinline__ long long load_idx(const void* p, long long e) {
-    if (ID == DGC_I32) return ((const DGC_GLB int32_t*)p)[e];
-    return ((const DGC_GLB int64_t*)p)[e];
-}
 
 // Where the runs come from: a table in the workspace (concatenated input), or the
 // packed allgather buffer itself (rank r's header holds its count) — the latter
@@ -164,15 +152,13 @@ struct RunSrc {
     // the header's count as gathered (packed mode, a part that has landed), unclamped
     __device__ __forceinline__ long long raw_count(int q) const {
         if (!payload || (parts > 1 && q % parts >= ready)) return 0;
-        return *reinterpret_cast<const long long*>(base_of(q));
+        return payload_count_raw(base_of(q));
     }
     __device__ __forceinline__ Run get_raw(int q) const {
         if (!payload) return table[q];
         const char* base = base_of(q);
         if (parts > 1 && q % parts >= ready) return Run{base + voff, base + ioff, 0};
-        long long c = *reinterpret_cast<const long long*>(base);
-        c = c < 0 ? 0 : (c > capacity ? capacity : c);
-        return Run{base + voff, base + ioff, c};
+        return Run{base + voff, base + ioff, payload_count(base, capacity)};
     }
     // split exchange: min over ranks of the smallest index in the parts after part p
     // (header word 1, dgc_payload_split); every index below it has landed with parts <= p
@@ -745,9 +731,6 @@ k_scatter_overflow(DecWS w, RunSrc rs, typename Out<OD>::T* __restrict__ grad, i
 }
 
 // ---------------------------------------------------------------- host side
-static int vbytes(int vd) { return vd == DGC_F32 ? 4 : 2; }   // F16, BF16: 2
-static int ibytes(int id) { return id == DGC_I32 ? 4 : 8; }
-
 // words zeroed by the dense fill's first block (a null pointer with a zero count skips)
 struct ZeroWords {
     int32_t* p[3];
@@ -884,22 +867,14 @@ static int run_scatter(const DecWS& w, const RunSrc& rs, typename Out<OD>::T* gr
 static int dispatch_scatter(int vd, int id, const DecWS& w, const RunSrc& rs, float* grad, int64_t n,
                             float scale, int max_runs, int dense, int64_t entries, int64_t run_cap, int runs,
                             hipStream_t s, const RunSrc* prev = nullptr) {
-    if (vd == DGC_F32 && id == DGC_I64)
-        return run_scatter<DGC_F32, DGC_I64>(w, rs, grad, n, scale, max_runs, dense, entries, run_cap, runs, s, prev);
-    if (vd == DGC_F32 && id == DGC_I32)
-        return run_scatter<DGC_F32, DGC_I32>(w, rs, grad, n, scale, max_runs, dense, entries, run_cap, runs, s, prev);
-    if (vd == DGC_F16 && id == DGC_I64)
-        return run_scatter<DGC_F16, DGC_I64>(w, rs, grad, n, scale, max_runs, dense, entries, run_cap, runs, s, prev);
-    if (vd == DGC_F16 && id == DGC_I32)
-        return run_scatter<DGC_F16, DGC_I32>(w, rs, grad, n, scale, max_runs, dense, entries, run_cap, runs, s, prev);
-    DGC_FAIL(DGC_ERR_DTYPE, "dgc_decompress: unsupported value/index dtype (%d, %d)", vd, id);
+    return with_vd(vd, [&](auto VD) { return with_id(id, [&](auto ID) {
+        return run_scatter<VD(), ID()>(w, rs, grad, n, scale, max_runs, dense, entries, run_cap, runs, s, prev); }); });
 }
 
 // wire_bf16: the call also takes bf16 wire values (the 16-bit split scatter)
 static int check_common(int vd, int id, const void* grad, int64_t n, void* ws, size_t ws_bytes, int runs,
                         int64_t sort_cap = 0, bool wire_bf16 = false) {
-    if ((vd != DGC_F32 && vd != DGC_F16 && !(wire_bf16 && vd == DGC_BF16)) || (id != DGC_I64 && id != DGC_I32))
-        DGC_FAIL(DGC_ERR_DTYPE, "dgc_decompress: unsupported value/index dtype (%d, %d)", vd, id);
+    DGC_TRY(check_wire("dgc_decompress", vd, id, wire_bf16));
     if (!grad || n < 1) DGC_FAIL(DGC_ERR_INVALID, "dgc_decompress: null grad or n < 1");
     if (runs < 1 || runs > kMaxRuns) DGC_FAIL(DGC_ERR_INVALID, "dgc_decompress: 1..%d runs supported", kMaxRuns);
     size_t need = 0;
@@ -934,10 +909,8 @@ int decompress(const void* values, int vd, const void* indices, int id, int64_t 
         DGC_LAUNCHED();
     } else {
         if (total > 1) {
-            if (id == DGC_I32)
-                hipLaunchKernelGGL(k_find_descents<DGC_I32>, dim3(grid_for(total)), dim3(kBlock), 0, s, ix, total, w);
-            else
-                hipLaunchKernelGGL(k_find_descents<DGC_I64>, dim3(grid_for(total)), dim3(kBlock), 0, s, ix, total, w);
+            with_id(id, [&](auto ID) {
+                hipLaunchKernelGGL(k_find_descents<ID()>, dim3(grid_for(total)), dim3(kBlock), 0, s, ix, total, w); });
             DGC_LAUNCHED();
         }
         hipLaunchKernelGGL(k_runs_from_descents, dim3(1), dim3(64), 0, s, w, v, ix, vbytes(vd), ibytes(id), total);
@@ -988,8 +961,7 @@ k_payload_split(const char* __restrict__ src, int64_t cap, int64_t voff, int64_t
     __shared__ unsigned long long smin[kMaxParts];
     if (threadIdx.x < kMaxParts) smin[threadIdx.x] = 0;
     __syncthreads();
-    long long cnt = *reinterpret_cast<const long long*>(src);
-    cnt = cnt < 0 ? 0 : (cnt > cap ? cap : cnt);
+    const long long cnt = payload_count(src, cap);
     for (long long e = (long long)blockIdx.x * kBlock + threadIdx.x; e < cnt; e += (long long)gridDim.x * kBlock) {
         const int p = (int)(e / pc);
         const long long j = e - (long long)p * pc;
@@ -1031,8 +1003,7 @@ k_payload_split(const char* __restrict__ src, int64_t cap, int64_t voff, int64_t
 }
 
 int payload_split(const void* payload, int64_t capacity, int parts, int vd, int id, void* split, hipStream_t s) {
-    if ((vd != DGC_F32 && vd != DGC_F16 && vd != DGC_BF16) || (id != DGC_I64 && id != DGC_I32))
-        DGC_FAIL(DGC_ERR_DTYPE, "dgc_payload_split: unsupported value/index dtype (%d, %d)", vd, id);
+    DGC_TRY(check_wire("dgc_payload_split", vd, id, true));
     if (!payload || !split || capacity < 0 || parts < 1 || parts > kMaxParts)
         DGC_FAIL(DGC_ERR_INVALID, "dgc_payload_split: null buffer, capacity < 0 or parts outside 1..%d", kMaxParts);
     if ((reinterpret_cast<uintptr_t>(payload) | reinterpret_cast<uintptr_t>(split)) & 255)
@@ -1045,23 +1016,14 @@ int payload_split(const void* payload, int64_t capacity, int parts, int vd, int 
     auto* tk = reinterpret_cast<uint32_t*>(pmin + kMaxParts);
     const unsigned g = (unsigned)grid_for(capacity, kBlock * 4);
     const char* src = static_cast<const char*>(payload);
-    const int vb = vbytes(vd);
     if (pc == 0) {   // no entries: headers only
         DGC_HIP(hipMemsetAsync(dst, 0, (size_t)parts * pbytes, s));
         return DGC_OK;
     }
-    if (vb == 2 && id == DGC_I32)
-        hipLaunchKernelGGL((k_payload_split<2, 4>), dim3(g), dim3(kBlock), 0, s, src, capacity, voff, ioff, dst, parts, pc,
-                           pbytes, pvoff, pioff, pmin, tk);
-    else if (vb == 2)
-        hipLaunchKernelGGL((k_payload_split<2, 8>), dim3(g), dim3(kBlock), 0, s, src, capacity, voff, ioff, dst, parts, pc,
-                           pbytes, pvoff, pioff, pmin, tk);
-    else if (id == DGC_I32)
-        hipLaunchKernelGGL((k_payload_split<4, 4>), dim3(g), dim3(kBlock), 0, s, src, capacity, voff, ioff, dst, parts, pc,
-                           pbytes, pvoff, pioff, pmin, tk);
-    else
-        hipLaunchKernelGGL((k_payload_split<4, 8>), dim3(g), dim3(kBlock), 0, s, src, capacity, voff, ioff, dst, parts, pc,
-                           pbytes, pvoff, pioff, pmin, tk);
+    // the copy goes by element width: bf16 and fp16 values are one kernel
+    with_bool(vbytes(vd) == 4, [&](auto V4) { with_id(id, [&](auto ID) {
+        hipLaunchKernelGGL((k_payload_split<V4() ? 4 : 2, ibytes(ID())>), dim3(g), dim3(kBlock), 0, s, src, capacity, voff,
+                           ioff, dst, parts, pc, pbytes, pvoff, pioff, pmin, tk); }); });
     DGC_LAUNCHED();
     return DGC_OK;
 }
@@ -1080,9 +1042,7 @@ static int check_split(const void* gathered, int32_t world, int parts, int64_t c
                        const char* fn, bool wire_bf16 = false) {
     if (!gathered || world < 1 || parts < 2 || parts > kMaxParts || capacity < 0 || world * parts > kMaxRuns)
         DGC_FAIL(DGC_ERR_INVALID, "%s: null buffer, parts outside 2..%d or world * parts > %d", fn, kMaxParts, kMaxRuns);
-    if ((vd != DGC_F32 && vd != DGC_F16 && !(wire_bf16 && vd == DGC_BF16)) || (id != DGC_I64 && id != DGC_I32))
-        DGC_FAIL(DGC_ERR_DTYPE, "%s: unsupported value/index dtype (%d, %d)", fn, vd, id);
-    return DGC_OK;
+    return check_wire(fn, vd, id, wire_bf16);
 }
 
 // Phase `part` of the split decompress (parts < part landed and scattered by the
@@ -1109,33 +1069,17 @@ int clear_split(const void* prev, int32_t world, int parts, int64_t capacity, in
     DGC_TRY(check_common(vd, id, grad, n, ws, ws_bytes, world * parts, pc));
     const DecWS w = carve_dec(ws, n, world * parts, pc);
     const RunSrc pr = split_src(prev, world, parts, parts, pbytes, pc, voff, ioff, nullptr);
-    return id == DGC_I32 ? launch_clear<DGC_I32>(pr, w, grad, n, s) : launch_clear<DGC_I64>(pr, w, grad, n, s);
+    return with_id(id, [&](auto ID) { return launch_clear<ID()>(pr, w, grad, n, s); });
 }
 
 // K6-16: phase `part` of the split decompress onto a bf16 / fp16 gradient that holds +0
 // (dgc_fill_zero16 before phase 0, which resets the status words). The phases, their
 // windows, the bounds, the regroup and both scatter paths are scatter_split's; the
 // kernels round to the dtype after every op and store 2-byte elements (Out<OD>).
-template <int OD, int VD>
-static int scatter16_id(int id, const DecWS& w, const RunSrc& rs, uint16_t* grad, int64_t n, float scale, int runs,
-                        int64_t pc, hipStream_t s) {
-    const int64_t entries = (int64_t)runs * pc;
-    return id == DGC_I32 ? run_scatter<VD, DGC_I32, OD>(w, rs, grad, n, scale, runs, kZeroNone, entries, pc, runs, s)
-                         : run_scatter<VD, DGC_I64, OD>(w, rs, grad, n, scale, runs, kZeroNone, entries, pc, runs, s);
-}
-
-template <int OD>
-static int scatter16_vd(int vd, int id, const DecWS& w, const RunSrc& rs, uint16_t* grad, int64_t n, float scale,
-                        int runs, int64_t pc, hipStream_t s) {
-    if (vd == DGC_F32) return scatter16_id<OD, DGC_F32>(id, w, rs, grad, n, scale, runs, pc, s);
-    if (vd == DGC_F16) return scatter16_id<OD, DGC_F16>(id, w, rs, grad, n, scale, runs, pc, s);
-    return scatter16_id<OD, DGC_BF16>(id, w, rs, grad, n, scale, runs, pc, s);
-}
-
 int scatter_split16(const void* gathered, int32_t world, int parts, int part, int64_t capacity, int vd, int id,
                     void* grad, int od, int64_t n, float scale, void* ws, size_t ws_bytes, hipStream_t s) {
     const char* fn = "dgc_scatter_split16";
-    if (od != DGC_BF16 && od != DGC_F16) DGC_FAIL(DGC_ERR_DTYPE, "%s: grad dtype must be DGC_BF16 or DGC_F16", fn);
+    DGC_TRY(check_h16(fn, od, "grad dtype"));
     DGC_TRY(check_split(gathered, world, parts, capacity, vd, id, fn, true));
     if (part < 0 || part >= parts) DGC_FAIL(DGC_ERR_INVALID, "%s: part %d outside 0..%d", fn, part, parts - 1);
     if (!grad || n < 1) DGC_FAIL(DGC_ERR_INVALID, "%s: null grad or n < 1", fn);
@@ -1146,8 +1090,9 @@ int scatter_split16(const void* gathered, int32_t world, int parts, int part, in
     const DecWS w = carve_dec(ws, n, world * parts, pc);
     const RunSrc rs = split_src(gathered, world, parts, part + 1, pbytes, pc, voff, ioff, &w);
     uint16_t* g = static_cast<uint16_t*>(grad);
-    return od == DGC_BF16 ? scatter16_vd<DGC_BF16>(vd, id, w, rs, g, n, scale, world * parts, pc, s)
-                          : scatter16_vd<DGC_F16>(vd, id, w, rs, g, n, scale, world * parts, pc, s);
+    const int runs = world * parts;
+    return with_h16(od, [&](auto OD) { return with_wire16(vd, [&](auto VD) { return with_id(id, [&](auto ID) {
+        return run_scatter<VD(), ID(), OD()>(w, rs, g, n, scale, runs, kZeroNone, (int64_t)runs * pc, pc, runs, s); }); }); });
 }
 
 int decompress_packed(const void* payload, int32_t world, int64_t rank_stride, int64_t capacity, int vd,
@@ -1185,7 +1130,7 @@ int clear_packed(const void* prev, int32_t world, int64_t rank_stride, int64_t c
     DecWS w = carve_dec(ws, n, world, capacity);
     const RunSrc pr{nullptr, nullptr, static_cast<const char*>(prev), rank_stride, voff, ioff, capacity, world,
                     nullptr, nullptr};
-    return id == DGC_I32 ? launch_clear<DGC_I32>(pr, w, grad, n, s) : launch_clear<DGC_I64>(pr, w, grad, n, s);
+    return with_id(id, [&](auto ID) { return launch_clear<ID()>(pr, w, grad, n, s); });
 }
 
 // Zero fill (the sparse scatter's precondition): one-shot workgroups, one 16-B

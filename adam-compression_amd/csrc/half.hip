@@ -29,7 +29,8 @@
 // is a template parameter of k_compensate16 (dgc_compensate16_clip) and of its multi-tensor
 // form k_compensate16_mt (dgc_compensate16_multi_clip: the batch's flat buffers with one
 // coefficient per tensor); DGC_CLIP_NONE is the unclipped kernel.
-#include "dgc_common.hpp"
+#include "dispatch.hpp"
+#include "payload.hpp"
 
 namespace dgc {
 
@@ -150,14 +151,7 @@ k_scatter16(const void* __restrict__ values, const I* __restrict__ idx, int64_t 
             raise_flag(bad);
             continue;
         }
-        float v;
-        if (VD == DGC_F32)
-            v = static_cast<const float*>(values)[q];
-        else if (VD == DGC_F16)
-            v = f16_to_f32(static_cast<const uint16_t*>(values)[q]);
-        else
-            v = bf16_to_f32(static_cast<const uint16_t*>(values)[q]);
-        v = round16<DT>(v);
+        const float v = round16<DT>(load_wire<VD>(values, q));
         out[i] = f32_to_h16<DT>(__fadd_rn(h16_to_f32<DT>(out[i]), v));
     }
 }
@@ -178,16 +172,8 @@ k_segsum16(const void* __restrict__ values, const I* __restrict__ idx, int64_t t
             continue;
         }
         float acc = 0.f;   // grad.zero_()
-        for (int64_t e = q; e < total && (int64_t)idx[e] == i0; ++e) {
-            float v;
-            if (VD == DGC_F32)
-                v = static_cast<const float*>(values)[e];
-            else if (VD == DGC_F16)
-                v = f16_to_f32(static_cast<const uint16_t*>(values)[e]);
-            else
-                v = bf16_to_f32(static_cast<const uint16_t*>(values)[e]);
-            acc = round16<DT>(__fadd_rn(acc, round16<DT>(v)));
-        }
+        for (int64_t e = q; e < total && (int64_t)idx[e] == i0; ++e)
+            acc = round16<DT>(__fadd_rn(acc, round16<DT>(load_wire<VD>(values, e))));
         out[i] = f32_to_h16<DT>(acc);
     }
 }
@@ -199,14 +185,12 @@ __global__ void __launch_bounds__(kBlock) k_scale16(uint16_t* __restrict__ x, in
 }
 
 // ---- the 16-bit batch (dgc_batch_desc.dtype): packed payloads, device counts ----
-int64_t payload_layout(int64_t capacity, int vd, int id, int64_t* voff, int64_t* ioff);   // decompress.hip
-
 // DGCSGDMemory.update of one packed payload's entries (its count in the header).
 template <typename I>
 __global__ void __launch_bounds__(kBlock)
 k_mask_packed16(const char* __restrict__ payload, int64_t ioff, uint16_t* __restrict__ mmt,
                 uint16_t* __restrict__ vec, int64_t n) {
-    const int64_t count = *reinterpret_cast<const int64_t*>(payload);
+    const int64_t count = payload_count_raw(payload);   // our own payload: as it stands
     const I* idx = reinterpret_cast<const I*>(payload + ioff);
     for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < count; q += (int64_t)gridDim.x * kBlock) {
         const int64_t i = (int64_t)idx[q];
@@ -222,7 +206,7 @@ template <int DT, int VD, typename I>
 __global__ void __launch_bounds__(kBlock)
 k_scatter_packed16(const char* __restrict__ run, int64_t capacity, int64_t voff, int64_t ioff,
                    uint16_t* __restrict__ out, int64_t n, int32_t* bad) {
-    int64_t count = *reinterpret_cast<const int64_t*>(run);
+    int64_t count = payload_count_raw(run);
     if (count < 0 || count > capacity) {   // a corrupted header: flag it (2), scatter none of it
         if (blockIdx.x == 0 && threadIdx.x == 0) raise_flag(bad, 2);
         count = 0;
@@ -235,14 +219,7 @@ k_scatter_packed16(const char* __restrict__ run, int64_t capacity, int64_t voff,
             raise_flag(bad);
             continue;
         }
-        float v;
-        if (VD == DGC_F32)
-            v = static_cast<const float*>(values)[q];
-        else if (VD == DGC_F16)
-            v = f16_to_f32(static_cast<const uint16_t*>(values)[q]);
-        else
-            v = bf16_to_f32(static_cast<const uint16_t*>(values)[q]);
-        v = round16<DT>(v);
+        const float v = round16<DT>(load_wire<VD>(values, q));
         out[i] = f32_to_h16<DT>(__fadd_rn(h16_to_f32<DT>(out[i]), v));
     }
 }
@@ -274,61 +251,6 @@ __global__ void __launch_bounds__(kBlock) k_gather16(G16Chunk c, uint16_t* __res
     }
 }
 
-static bool is16(int32_t dt) { return dt == DGC_BF16 || dt == DGC_F16; }
-
-template <int DT, typename I>
-static int segsum16_t(const void* values, int32_t vd, const I* idx, int64_t total, uint16_t* out, int64_t n,
-                      int32_t* bad, hipStream_t s) {
-    if (total <= 0) return DGC_OK;
-    const int grid = grid_for(total);
-    if (vd == DGC_F32)
-        hipLaunchKernelGGL((k_segsum16<DT, DGC_F32, I>), dim3(grid), dim3(kBlock), 0, s, values, idx, total, out, n, bad);
-    else if (vd == DGC_F16)
-        hipLaunchKernelGGL((k_segsum16<DT, DGC_F16, I>), dim3(grid), dim3(kBlock), 0, s, values, idx, total, out, n, bad);
-    else
-        hipLaunchKernelGGL((k_segsum16<DT, DGC_BF16, I>), dim3(grid), dim3(kBlock), 0, s, values, idx, total, out, n, bad);
-    DGC_LAUNCHED();
-    return DGC_OK;
-}
-
-template <int DT, bool NEST, bool ACC>
-static void compensate16_clip_t(int32_t kind, int grid, hipStream_t s, const uint16_t* g, uint16_t* m, uint16_t* v,
-                                uint16_t* o, float* v32, int64_t n, float mom, ClipArg ca) {
-    if (kind == DGC_CLIP_SCALE)
-        hipLaunchKernelGGL((k_compensate16<DT, NEST, ACC, DGC_CLIP_SCALE>), dim3(grid), dim3(kBlock), 0, s, g, m, v, o, v32, n, mom, ca);
-    else if (kind == DGC_CLIP_CLAMP)
-        hipLaunchKernelGGL((k_compensate16<DT, NEST, ACC, DGC_CLIP_CLAMP>), dim3(grid), dim3(kBlock), 0, s, g, m, v, o, v32, n, mom, ca);
-    else
-        hipLaunchKernelGGL((k_compensate16<DT, NEST, ACC, DGC_CLIP_NONE>), dim3(grid), dim3(kBlock), 0, s, g, m, v, o, v32, n, mom, ca);
-}
-
-template <int DT>
-static int compensate16_t(const uint16_t* g, uint16_t* m, uint16_t* v, uint16_t* o, float* v32, int64_t n,
-                          float mom, bool nest, bool acc, int32_t kind, ClipArg ca, hipStream_t s) {
-    const int grid = grid_for(n);
-    if (nest && acc)
-        compensate16_clip_t<DT, true, true>(kind, grid, s, g, m, v, o, v32, n, mom, ca);
-    else if (nest)
-        compensate16_clip_t<DT, true, false>(kind, grid, s, g, m, v, o, v32, n, mom, ca);
-    else if (acc)
-        compensate16_clip_t<DT, false, true>(kind, grid, s, g, m, v, o, v32, n, mom, ca);
-    else
-        compensate16_clip_t<DT, false, false>(kind, grid, s, g, m, v, o, v32, n, mom, ca);
-    DGC_LAUNCHED();
-    return DGC_OK;
-}
-
-template <int DT, bool NEST>
-static void compensate16_mt_t(int32_t kind, dim3 gd, hipStream_t s, const C16Chunk& c, const uint16_t* g, uint16_t* m,
-                              uint16_t* v, float* v32, float mom, ClipArg ca) {
-    if (kind == DGC_CLIP_SCALE)
-        hipLaunchKernelGGL((k_compensate16_mt<DT, NEST, DGC_CLIP_SCALE>), gd, dim3(kBlock), 0, s, c, g, m, v, v32, mom, ca);
-    else if (kind == DGC_CLIP_CLAMP)
-        hipLaunchKernelGGL((k_compensate16_mt<DT, NEST, DGC_CLIP_CLAMP>), gd, dim3(kBlock), 0, s, c, g, m, v, v32, mom, ca);
-    else
-        hipLaunchKernelGGL((k_compensate16_mt<DT, NEST, DGC_CLIP_NONE>), gd, dim3(kBlock), 0, s, c, g, m, v, v32, mom, ca);
-}
-
 // one chunk (<= kC16Max tensors from t0) of the table, checked
 static int compensate16_mt_chunk(const int64_t* numels, const int64_t* offsets, int32_t t0, int32_t count,
                                  int64_t flat_numel, C16Chunk& c, int64_t& blocks) {
@@ -352,35 +274,11 @@ static int compensate16_mt_chunk(const int64_t* numels, const int64_t* offsets, 
     return DGC_OK;
 }
 
-static int clip16_check(int32_t kind, const float* clip, const char* who) {
-    if (!clip_kind_ok(kind)) DGC_FAIL(DGC_ERR_INVALID, "%s: clip kind %d", who, (int)kind);
-    if (kind == DGC_CLIP_SCALE && !clip) DGC_FAIL(DGC_ERR_INVALID, "%s: DGC_CLIP_SCALE needs the coefficient table", who);
-    return DGC_OK;
-}
-
-template <int DT, typename I>
-static int scatter16_t(const void* values, int32_t vd, const I* idx, const int64_t* offs, int32_t nruns,
-                       uint16_t* out, int64_t n, int32_t* bad, hipStream_t s) {
-    for (int32_t r = 0; r < nruns; ++r) {   // rank order: one launch per run
-        const int64_t b = offs[r], e = offs[r + 1];
-        if (e <= b) continue;
-        const int grid = grid_for(e - b);
-        if (vd == DGC_F32)
-            hipLaunchKernelGGL((k_scatter16<DT, DGC_F32, I>), dim3(grid), dim3(kBlock), 0, s, values, idx, b, e, out, n, bad);
-        else if (vd == DGC_F16)
-            hipLaunchKernelGGL((k_scatter16<DT, DGC_F16, I>), dim3(grid), dim3(kBlock), 0, s, values, idx, b, e, out, n, bad);
-        else
-            hipLaunchKernelGGL((k_scatter16<DT, DGC_BF16, I>), dim3(grid), dim3(kBlock), 0, s, values, idx, b, e, out, n, bad);
-        DGC_LAUNCHED();
-    }
-    return DGC_OK;
-}
-
 static int compensate16(const char* who, const void* grad, void* mmt, void* vec, void* out, float* vec32, int64_t n,
                         float momentum, int32_t nesterov, int32_t accumulate, int32_t dtype, int32_t kind,
                         const float* clip, float clip_value, void* stream) {
-    if (!is16(dtype)) DGC_FAIL(DGC_ERR_DTYPE, "%s: dtype must be DGC_BF16 or DGC_F16", who);
-    DGC_TRY(clip16_check(kind, clip, who));
+    DGC_TRY(check_h16(who, dtype));
+    DGC_TRY(check_clip(who, kind, clip));
     if (n < 0) DGC_FAIL(DGC_ERR_INVALID, "%s: n < 0", who);
     if (n == 0) return DGC_OK;
     if (!grad || !mmt) DGC_FAIL(DGC_ERR_INVALID, "%s: null grad/mmt", who);
@@ -392,10 +290,23 @@ static int compensate16(const char* who, const void* grad, void* mmt, void* vec,
     auto o = static_cast<uint16_t*>(out);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const ClipArg ca{clip, clip_value};
-    return dtype == DGC_BF16
-               ? compensate16_t<DGC_BF16>(g, m, v, o, vec32, n, momentum, nesterov != 0, accumulate != 0, kind, ca, s)
-               : compensate16_t<DGC_F16>(g, m, v, o, vec32, n, momentum, nesterov != 0, accumulate != 0, kind, ca, s);
+    with_h16(dtype, [&](auto DT) { with_bool(nesterov != 0, [&](auto NEST) { with_bool(accumulate != 0, [&](auto ACC) {
+        with_clip(kind, [&](auto CLIP) {
+            hipLaunchKernelGGL((k_compensate16<DT(), NEST(), ACC(), CLIP()>), dim3(grid_for(n)), dim3(kBlock), 0, s, g, m,
+                               v, o, vec32, n, momentum, ca); }); }); }); });
+    DGC_LAUNCHED();
+    return DGC_OK;
 }
+
+// grad.mul_(1 / W), rounded to the dtype; x 1.0 is the identity in every dtype
+static int scale16(int32_t dtype, uint16_t* x, int64_t n, float scale, hipStream_t s) {
+    if (scale == 1.0f) return DGC_OK;
+    with_h16(dtype, [&](auto DT) {
+        hipLaunchKernelGGL(k_scale16<DT()>, dim3(grid_for(n)), dim3(kBlock), 0, s, x, n, scale); });
+    DGC_LAUNCHED();
+    return DGC_OK;
+}
+
 }  // namespace dgc
 
 extern "C" int dgc_compensate16(const void* grad, void* mmt, void* vec, void* out, float* vec32, int64_t n,
@@ -417,8 +328,8 @@ extern "C" int dgc_compensate16_multi_clip(const void* grad, void* mmt, void* ve
                                            int32_t clip_kind, const float* clip, float clip_value, void* stream) {
     using namespace dgc;
     const char* who = "dgc_compensate16_multi_clip";
-    if (!is16(dtype)) DGC_FAIL(DGC_ERR_DTYPE, "%s: dtype must be DGC_BF16 or DGC_F16", who);
-    DGC_TRY(clip16_check(clip_kind, clip, who));
+    DGC_TRY(check_h16(who, dtype));
+    DGC_TRY(check_clip(who, clip_kind, clip));
     if (count < 0 || flat_numel < 0) DGC_FAIL(DGC_ERR_INVALID, "%s: count or flat_numel < 0", who);
     if (count == 0) return DGC_OK;
     if (!grad || !mmt || !vec || !numels || !offsets) DGC_FAIL(DGC_ERR_INVALID, "%s: null argument", who);
@@ -435,13 +346,9 @@ extern "C" int dgc_compensate16_multi_clip(const void* grad, void* mmt, void* ve
         DGC_TRY(compensate16_mt_chunk(numels, offsets, t0, count, flat_numel, c, blocks));
         if (blocks == 0) continue;
         const dim3 gd((unsigned)blocks);
-        if (dtype == DGC_BF16) {
-            if (nesterov) compensate16_mt_t<DGC_BF16, true>(clip_kind, gd, s, c, g, m, v, vec32, momentum, ca);
-            else compensate16_mt_t<DGC_BF16, false>(clip_kind, gd, s, c, g, m, v, vec32, momentum, ca);
-        } else {
-            if (nesterov) compensate16_mt_t<DGC_F16, true>(clip_kind, gd, s, c, g, m, v, vec32, momentum, ca);
-            else compensate16_mt_t<DGC_F16, false>(clip_kind, gd, s, c, g, m, v, vec32, momentum, ca);
-        }
+        with_h16(dtype, [&](auto DT) { with_bool(nesterov != 0, [&](auto NEST) { with_clip(clip_kind, [&](auto CLIP) {
+            hipLaunchKernelGGL((k_compensate16_mt<DT(), NEST(), CLIP()>), gd, dim3(kBlock), 0, s, c, g, m, v, vec32,
+                               momentum, ca); }); }); });
         DGC_LAUNCHED();
     }
     return DGC_OK;
@@ -449,14 +356,12 @@ extern "C" int dgc_compensate16_multi_clip(const void* grad, void* mmt, void* ve
 
 extern "C" int dgc_widen16(const void* x, float* y, int64_t n, int32_t dtype, void* stream) {
     using namespace dgc;
-    if (!is16(dtype)) DGC_FAIL(DGC_ERR_DTYPE, "dgc_widen16: dtype must be DGC_BF16 or DGC_F16");
+    DGC_TRY(check_h16("dgc_widen16", dtype));
     if (n < 0 || (n > 0 && (!x || !y))) DGC_FAIL(DGC_ERR_INVALID, "dgc_widen16: bad arguments");
     if (n == 0) return DGC_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == DGC_BF16)
-        hipLaunchKernelGGL(k_widen16<DGC_BF16>, dim3(grid_for(n)), dim3(kBlock), 0, s, static_cast<const uint16_t*>(x), y, n);
-    else
-        hipLaunchKernelGGL(k_widen16<DGC_F16>, dim3(grid_for(n)), dim3(kBlock), 0, s, static_cast<const uint16_t*>(x), y, n);
+    with_h16(dtype, [&](auto DT) {
+        hipLaunchKernelGGL(k_widen16<DT()>, dim3(grid_for(n)), dim3(kBlock), 0, s, static_cast<const uint16_t*>(x), y, n); });
     DGC_LAUNCHED();
     return DGC_OK;
 }
@@ -465,17 +370,15 @@ extern "C" int dgc_mask_indices16(void* mmt, void* vec, int64_t n, const void* i
                                   int32_t* bad_flag, void* stream) {
     using namespace dgc;
     if (!vec || (count > 0 && !indices) || !bad_flag) DGC_FAIL(DGC_ERR_INVALID, "dgc_mask_indices16: null argument");
-    if (idtype != DGC_I64 && idtype != DGC_I32) DGC_FAIL(DGC_ERR_DTYPE, "dgc_mask_indices16: index dtype");
+    if (!index_ok(idtype)) DGC_FAIL(DGC_ERR_DTYPE, "dgc_mask_indices16: index dtype");
     if (count <= 0) return DGC_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto m = static_cast<uint16_t*>(mmt);
     auto v = static_cast<uint16_t*>(vec);
-    if (idtype == DGC_I32)
-        hipLaunchKernelGGL(k_mask16<int32_t>, dim3(grid_for(count)), dim3(kBlock), 0, s, m, v,
-                           static_cast<const int32_t*>(indices), count, n, bad_flag);
-    else
-        hipLaunchKernelGGL(k_mask16<int64_t>, dim3(grid_for(count)), dim3(kBlock), 0, s, m, v,
-                           static_cast<const int64_t*>(indices), count, n, bad_flag);
+    with_id(idtype, [&](auto ID) {
+        using I = idx_t<decltype(ID)>;
+        hipLaunchKernelGGL(k_mask16<I>, dim3(grid_for(count)), dim3(kBlock), 0, s, m, v, static_cast<const I*>(indices),
+                           count, n, bad_flag); });
     DGC_LAUNCHED();
     return DGC_OK;
 }
@@ -484,10 +387,9 @@ extern "C" int dgc_decompress16(const void* values, int32_t vdtype, const void* 
                                 const int64_t* run_offsets, int32_t nruns, void* grad, int32_t dtype, int64_t n,
                                 float scale, int32_t* bad_flag, void* stream) {
     using namespace dgc;
-    if (!is16(dtype)) DGC_FAIL(DGC_ERR_DTYPE, "dgc_decompress16: grad dtype must be DGC_BF16 or DGC_F16");
-    if (vdtype != DGC_F32 && vdtype != DGC_F16 && vdtype != DGC_BF16)
-        DGC_FAIL(DGC_ERR_DTYPE, "dgc_decompress16: value dtype");
-    if (idtype != DGC_I64 && idtype != DGC_I32) DGC_FAIL(DGC_ERR_DTYPE, "dgc_decompress16: index dtype");
+    DGC_TRY(check_h16("dgc_decompress16", dtype, "grad dtype"));
+    if (!wire_ok(vdtype, true)) DGC_FAIL(DGC_ERR_DTYPE, "dgc_decompress16: value dtype");
+    if (!index_ok(idtype)) DGC_FAIL(DGC_ERR_DTYPE, "dgc_decompress16: index dtype");
     const bool sorted = nruns == -1;   // one stably index-sorted run: run_offsets = {0, total}
     if (sorted) nruns = 1;
     if (!grad || n < 0 || nruns < 0 || (nruns > 0 && !run_offsets) || !bad_flag)
@@ -502,44 +404,33 @@ extern "C" int dgc_decompress16(const void* values, int32_t vdtype, const void* 
     auto out = static_cast<uint16_t*>(grad);
     hipLaunchKernelGGL(k_zero16, dim3(grid_for(n)), dim3(kBlock), 0, s, out, n);   // grad.zero_()
     DGC_LAUNCHED();
-    if (sorted) {
-        const int64_t total = run_offsets[1] - run_offsets[0];
-        const char* vb = static_cast<const char*>(values) + run_offsets[0] * (vdtype == DGC_F32 ? 4 : 2);
-        const char* ib = static_cast<const char*>(indices) + run_offsets[0] * (idtype == DGC_I32 ? 4 : 8);
-        if (dtype == DGC_BF16 && idtype == DGC_I32)
-            DGC_TRY(segsum16_t<DGC_BF16>(vb, vdtype, reinterpret_cast<const int32_t*>(ib), total, out, n, bad_flag, s));
-        else if (dtype == DGC_BF16)
-            DGC_TRY(segsum16_t<DGC_BF16>(vb, vdtype, reinterpret_cast<const int64_t*>(ib), total, out, n, bad_flag, s));
-        else if (idtype == DGC_I32)
-            DGC_TRY(segsum16_t<DGC_F16>(vb, vdtype, reinterpret_cast<const int32_t*>(ib), total, out, n, bad_flag, s));
-        else
-            DGC_TRY(segsum16_t<DGC_F16>(vb, vdtype, reinterpret_cast<const int64_t*>(ib), total, out, n, bad_flag, s));
-    } else if (dtype == DGC_BF16) {
-        if (idtype == DGC_I32)
-            DGC_TRY(scatter16_t<DGC_BF16>(values, vdtype, static_cast<const int32_t*>(indices), run_offsets, nruns, out, n, bad_flag, s));
-        else
-            DGC_TRY(scatter16_t<DGC_BF16>(values, vdtype, static_cast<const int64_t*>(indices), run_offsets, nruns, out, n, bad_flag, s));
-    } else {
-        if (idtype == DGC_I32)
-            DGC_TRY(scatter16_t<DGC_F16>(values, vdtype, static_cast<const int32_t*>(indices), run_offsets, nruns, out, n, bad_flag, s));
-        else
-            DGC_TRY(scatter16_t<DGC_F16>(values, vdtype, static_cast<const int64_t*>(indices), run_offsets, nruns, out, n, bad_flag, s));
-    }
-    if (scale != 1.0f) {   // grad.mul_(1 / W); x 1.0 is the identity in every dtype
-        if (dtype == DGC_BF16)
-            hipLaunchKernelGGL(k_scale16<DGC_BF16>, dim3(grid_for(n)), dim3(kBlock), 0, s, out, n, scale);
-        else
-            hipLaunchKernelGGL(k_scale16<DGC_F16>, dim3(grid_for(n)), dim3(kBlock), 0, s, out, n, scale);
-        DGC_LAUNCHED();
-    }
-    return DGC_OK;
+    DGC_TRY(with_h16(dtype, [&](auto DT) { return with_wire16(vdtype, [&](auto VD) { return with_id(idtype, [&](auto ID) -> int {
+        using I = idx_t<decltype(ID)>;
+        auto idx = static_cast<const I*>(indices);
+        if (sorted) {
+            const int64_t b = run_offsets[0], total = run_offsets[1] - b;
+            if (total <= 0) return DGC_OK;
+            hipLaunchKernelGGL((k_segsum16<DT(), VD(), I>), dim3(grid_for(total)), dim3(kBlock), 0, s,
+                               static_cast<const char*>(values) + b * vbytes(vdtype), idx + b, total, out, n, bad_flag);
+            DGC_LAUNCHED();
+        } else {
+            for (int32_t r = 0; r < nruns; ++r) {   // rank order: one launch per run
+                const int64_t b = run_offsets[r], e = run_offsets[r + 1];
+                if (e <= b) continue;
+                hipLaunchKernelGGL((k_scatter16<DT(), VD(), I>), dim3(grid_for(e - b)), dim3(kBlock), 0, s, values, idx, b, e,
+                                   out, n, bad_flag);
+                DGC_LAUNCHED();
+            }
+        }
+        return DGC_OK; }); }); }));
+    return scale16(dtype, out, n, scale, s);
 }
 
 extern "C" int dgc_mask_packed16(const void* payload, int64_t capacity, int32_t vdtype, int32_t idtype, void* mmt,
                                  void* vec, int64_t n, void* stream) {
     using namespace dgc;
     if (!payload || !vec || capacity < 0 || n < 0) DGC_FAIL(DGC_ERR_INVALID, "dgc_mask_packed16: bad arguments");
-    if (idtype != DGC_I64 && idtype != DGC_I32) DGC_FAIL(DGC_ERR_DTYPE, "dgc_mask_packed16: index dtype");
+    if (!index_ok(idtype)) DGC_FAIL(DGC_ERR_DTYPE, "dgc_mask_packed16: index dtype");
     if (capacity == 0) return DGC_OK;
     int64_t voff = 0, ioff = 0;
     payload_layout(capacity, vdtype, idtype, &voff, &ioff);
@@ -548,41 +439,19 @@ extern "C" int dgc_mask_packed16(const void* payload, int64_t capacity, int32_t 
     auto p = static_cast<const char*>(payload);
     auto m = static_cast<uint16_t*>(mmt);
     auto v = static_cast<uint16_t*>(vec);
-    if (idtype == DGC_I32)
-        hipLaunchKernelGGL(k_mask_packed16<int32_t>, dim3(grid), dim3(kBlock), 0, s, p, ioff, m, v, n);
-    else
-        hipLaunchKernelGGL(k_mask_packed16<int64_t>, dim3(grid), dim3(kBlock), 0, s, p, ioff, m, v, n);
+    with_id(idtype, [&](auto ID) {
+        hipLaunchKernelGGL(k_mask_packed16<idx_t<decltype(ID)>>, dim3(grid), dim3(kBlock), 0, s, p, ioff, m, v, n); });
     DGC_LAUNCHED();
     return DGC_OK;
 }
-
-namespace dgc {
-template <int DT, typename I>
-static int scatter_packed16_t(const char* p, int32_t world, int64_t stride, int64_t capacity, int32_t vd, int64_t voff,
-                              int64_t ioff, uint16_t* out, int64_t n, int32_t* bad, hipStream_t s) {
-    const int grid = grid_for(capacity);
-    for (int32_t r = 0; r < world; ++r) {   // rank order: one launch per run
-        const char* run = p + (int64_t)r * stride;
-        if (vd == DGC_F32)
-            hipLaunchKernelGGL((k_scatter_packed16<DT, DGC_F32, I>), dim3(grid), dim3(kBlock), 0, s, run, capacity, voff, ioff, out, n, bad);
-        else if (vd == DGC_F16)
-            hipLaunchKernelGGL((k_scatter_packed16<DT, DGC_F16, I>), dim3(grid), dim3(kBlock), 0, s, run, capacity, voff, ioff, out, n, bad);
-        else
-            hipLaunchKernelGGL((k_scatter_packed16<DT, DGC_BF16, I>), dim3(grid), dim3(kBlock), 0, s, run, capacity, voff, ioff, out, n, bad);
-        DGC_LAUNCHED();
-    }
-    return DGC_OK;
-}
-}  // namespace dgc
 
 extern "C" int dgc_decompress_packed16(const void* payload, int32_t world, int64_t rank_stride, int64_t capacity,
                                        int32_t vdtype, int32_t idtype, void* grad, int32_t dtype, int64_t n,
                                        float scale, int32_t* bad_flag, void* stream) {
     using namespace dgc;
-    if (!is16(dtype)) DGC_FAIL(DGC_ERR_DTYPE, "dgc_decompress_packed16: grad dtype must be DGC_BF16 or DGC_F16");
-    if (vdtype != DGC_F32 && vdtype != DGC_F16 && vdtype != DGC_BF16)
-        DGC_FAIL(DGC_ERR_DTYPE, "dgc_decompress_packed16: value dtype");
-    if (idtype != DGC_I64 && idtype != DGC_I32) DGC_FAIL(DGC_ERR_DTYPE, "dgc_decompress_packed16: index dtype");
+    DGC_TRY(check_h16("dgc_decompress_packed16", dtype, "grad dtype"));
+    if (!wire_ok(vdtype, true)) DGC_FAIL(DGC_ERR_DTYPE, "dgc_decompress_packed16: value dtype");
+    if (!index_ok(idtype)) DGC_FAIL(DGC_ERR_DTYPE, "dgc_decompress_packed16: index dtype");
     if (!payload || !grad || !bad_flag || world < 1 || capacity < 0 || n < 0)
         DGC_FAIL(DGC_ERR_INVALID, "dgc_decompress_packed16: bad arguments");
     int64_t voff = 0, ioff = 0;
@@ -595,24 +464,14 @@ extern "C" int dgc_decompress_packed16(const void* payload, int32_t world, int64
     hipLaunchKernelGGL(k_zero16, dim3(grid_for(n)), dim3(kBlock), 0, s, out, n);   // grad.zero_()
     DGC_LAUNCHED();
     auto p = static_cast<const char*>(payload);
-    if (capacity > 0) {
-        if (dtype == DGC_BF16 && idtype == DGC_I32)
-            DGC_TRY((scatter_packed16_t<DGC_BF16, int32_t>(p, world, rank_stride, capacity, vdtype, voff, ioff, out, n, bad_flag, s)));
-        else if (dtype == DGC_BF16)
-            DGC_TRY((scatter_packed16_t<DGC_BF16, int64_t>(p, world, rank_stride, capacity, vdtype, voff, ioff, out, n, bad_flag, s)));
-        else if (idtype == DGC_I32)
-            DGC_TRY((scatter_packed16_t<DGC_F16, int32_t>(p, world, rank_stride, capacity, vdtype, voff, ioff, out, n, bad_flag, s)));
-        else
-            DGC_TRY((scatter_packed16_t<DGC_F16, int64_t>(p, world, rank_stride, capacity, vdtype, voff, ioff, out, n, bad_flag, s)));
-    }
-    if (scale != 1.0f) {   // grad.mul_(1 / W), rounded to the dtype
-        if (dtype == DGC_BF16)
-            hipLaunchKernelGGL(k_scale16<DGC_BF16>, dim3(grid_for(n)), dim3(kBlock), 0, s, out, n, scale);
-        else
-            hipLaunchKernelGGL(k_scale16<DGC_F16>, dim3(grid_for(n)), dim3(kBlock), 0, s, out, n, scale);
-        DGC_LAUNCHED();
-    }
-    return DGC_OK;
+    DGC_TRY(with_h16(dtype, [&](auto DT) { return with_wire16(vdtype, [&](auto VD) { return with_id(idtype, [&](auto ID) -> int {
+        for (int32_t r = 0; r < world && capacity > 0; ++r) {   // rank order: one launch per run
+            hipLaunchKernelGGL((k_scatter_packed16<DT(), VD(), idx_t<decltype(ID)>>), dim3(grid_for(capacity)), dim3(kBlock),
+                               0, s, p + (int64_t)r * rank_stride, capacity, voff, ioff, out, n, bad_flag);
+            DGC_LAUNCHED();
+        }
+        return DGC_OK; }); }); }));
+    return scale16(dtype, out, n, scale, s);
 }
 
 extern "C" int dgc_gather16(const void* const* srcs, const int64_t* numels, const int64_t* offsets, int32_t count,

@@ -52,6 +52,8 @@
 #include <cmath>
 #include <vector>
 
+#include "dispatch.hpp"             // with_*: run-time dtype / flag -> template argument
+#include "payload.hpp"              // payload layout, shared argument checks
 #include "select_types.hpp"        // constants, list slots, TDesc / SelState / SetG / SelCfg / SelWS
 #include "select_layout.hpp"       // host layout, workspace carve, k_put_one / k_put_starts
 #include "select_tiles.hpp"        // tile loads, list append, task(), deferred masking
@@ -66,8 +68,6 @@
 #include "select_nth.hpp"          // K5 k_nth_select
 
 namespace dgc {
-
-int64_t payload_layout(int64_t capacity, int vd, int id, int64_t* voff, int64_t* ioff);   // decompress.hip
 
 __global__ void k_spec_reset(float* spec, int32_t T) {
     for (int i = threadIdx.x; i < kSpecWords * T; i += blockDim.x) spec[i] = __builtin_huge_valf();
@@ -97,11 +97,9 @@ static int validate_select(const dgc_select_params* p, void* values, void* indic
     if (p->num_samples < 1 || p->num_samples > p->numel)
         DGC_FAIL(DGC_ERR_INVALID, "dgc_select: bad num_samples");
     if (p->max_iters < 0) DGC_FAIL(DGC_ERR_INVALID, "dgc_select: max_iters < 0");
-    if (p->vdtype != DGC_F32 && p->vdtype != DGC_F16 && p->vdtype != DGC_BF16)
-        DGC_FAIL(DGC_ERR_DTYPE, "dgc_select: value dtype");
-    if (p->thr_dtype != DGC_F32 && p->thr_dtype != DGC_F16 && p->thr_dtype != DGC_BF16)
-        DGC_FAIL(DGC_ERR_DTYPE, "dgc_select: threshold dtype");
-    if (p->idtype != DGC_I64 && p->idtype != DGC_I32) DGC_FAIL(DGC_ERR_DTYPE, "dgc_select: index dtype");
+    if (!wire_ok(p->vdtype, true)) DGC_FAIL(DGC_ERR_DTYPE, "dgc_select: value dtype");
+    if (!float_dtype_ok(p->thr_dtype)) DGC_FAIL(DGC_ERR_DTYPE, "dgc_select: threshold dtype");
+    if (!index_ok(p->idtype)) DGC_FAIL(DGC_ERR_DTYPE, "dgc_select: index dtype");
     if (p->idtype == DGC_I32 && p->numel > 2147483647LL)
         DGC_FAIL(DGC_ERR_OVERFLOW, "dgc_select: int32 indices cannot address %lld elements",
                  (long long)p->numel);
@@ -574,33 +572,18 @@ constexpr unsigned kK1FlatLds = 48u << 10;
 // tensor can take them.
 static bool k1_stride_ok(bool sampled, int64_t stride) { return !sampled || (stride >= 4 && stride < (1LL << 30)); }
 
-template <bool NEST, bool ONE, typename... Args>
-static void launch_k1_clip(int32_t clip_kind, unsigned lds, dim3 gd, hipStream_t s, Args... args) {
-    if (clip_kind == DGC_CLIP_SCALE)
-        hipLaunchKernelGGL((k_compensate_list<NEST, ONE, DGC_CLIP_SCALE>), gd, dim3(kBlock), lds, s, args...);
-    else if (clip_kind == DGC_CLIP_CLAMP)
-        hipLaunchKernelGGL((k_compensate_list<NEST, ONE, DGC_CLIP_CLAMP>), gd, dim3(kBlock), lds, s, args...);
-    else
-        hipLaunchKernelGGL((k_compensate_list<NEST, ONE, DGC_CLIP_NONE>), gd, dim3(kBlock), lds, s, args...);
-}
-
+// K1 of one tensor (ONE: the flat bucket) or of a batch; the two callers differ in the tables they pass.
 template <bool ONE, typename... Args>
 static void launch_k1(bool nesterov, int32_t clip_kind, unsigned lds, dim3 gd, hipStream_t s, Args... args) {
-    if (nesterov) launch_k1_clip<true, ONE>(clip_kind, lds, gd, s, args...);
-    else launch_k1_clip<false, ONE>(clip_kind, lds, gd, s, args...);
-}
-
-static int k1_clip_check(int32_t kind, const float* clip, const char* who) {
-    if (!clip_kind_ok(kind)) DGC_FAIL(DGC_ERR_INVALID, "%s: clip kind %d", who, (int)kind);
-    if (kind == DGC_CLIP_SCALE && !clip) DGC_FAIL(DGC_ERR_INVALID, "%s: DGC_CLIP_SCALE needs the coefficient table", who);
-    return DGC_OK;
+    with_bool(nesterov, [&](auto NEST) { with_clip(clip_kind, [&](auto CLIP) {
+        hipLaunchKernelGGL((k_compensate_list<NEST(), ONE, CLIP()>), gd, dim3(kBlock), lds, s, args...); }); });
 }
 
 int compress_begin(const float* grad, float* mmt, float* vec, float momentum, bool nesterov, int64_t s_start,
                    int64_t s_stride, const dgc_select_params* p, float* spec, void* ws, size_t ws_bytes,
                    hipStream_t s, int32_t clip_kind = DGC_CLIP_NONE, ClipArg ca = ClipArg{nullptr, 0.f}) {
     DGC_TRY(compress_check(p, nullptr, nullptr, s_start, s_stride, 1, false));
-    DGC_TRY(k1_clip_check(clip_kind, ca.tab, "dgc_compress"));
+    DGC_TRY(check_clip("dgc_compress", clip_kind, ca.tab));
     if (!grad || !mmt || !vec) DGC_FAIL(DGC_ERR_INVALID, "dgc_compress: null grad/mmt/vec");
     Layout L;
     SelWS w;
@@ -653,33 +636,14 @@ int compress_begin(const float* grad, float* mmt, float* vec, float momentum, bo
 // dgc_compress_finish(vec32, null, ...) then serves the image. mmt, vec and vec32 hold
 // ceil(numel / 1024) * 1024 elements. There is no unfused fallback: what the listing
 // kernel cannot take is refused.
-template <int DT, bool NEST, typename... Args>
-static void launch_k1_16_clip(int32_t clip_kind, dim3 gd, hipStream_t s, Args... args) {
-    if (clip_kind == DGC_CLIP_SCALE)
-        hipLaunchKernelGGL((k_compensate_list16<DT, NEST, DGC_CLIP_SCALE>), gd, dim3(kBlock), 0, s, args...);
-    else if (clip_kind == DGC_CLIP_CLAMP)
-        hipLaunchKernelGGL((k_compensate_list16<DT, NEST, DGC_CLIP_CLAMP>), gd, dim3(kBlock), 0, s, args...);
-    else
-        hipLaunchKernelGGL((k_compensate_list16<DT, NEST, DGC_CLIP_NONE>), gd, dim3(kBlock), 0, s, args...);
-}
-
-template <int DT>
-static void launch_k1_16(bool nesterov, int32_t clip_kind, dim3 gd, hipStream_t s, const uint16_t* grad,
-                         uint16_t* mmt, uint16_t* vec, float* vec32, float momentum, const SelWS& w, int64_t start,
-                         int wt, const OneTable& ot, ClipArg ca) {
-    if (nesterov) launch_k1_16_clip<DT, true>(clip_kind, gd, s, grad, mmt, vec, vec32, momentum, w, start, wt, ot, ca);
-    else launch_k1_16_clip<DT, false>(clip_kind, gd, s, grad, mmt, vec, vec32, momentum, w, start, wt, ot, ca);
-}
-
 int compress_begin16(const void* grad, void* mmt, void* vec, float* vec32, float momentum, bool nesterov,
                      int64_t s_start, int64_t s_stride, const dgc_select_params* p, float* spec, void* ws,
                      size_t ws_bytes, int32_t dtype, hipStream_t s, int32_t clip_kind = DGC_CLIP_NONE,
                      ClipArg ca = ClipArg{nullptr, 0.f}, const char* who = "dgc_compress_begin16") {
-    if (dtype != DGC_BF16 && dtype != DGC_F16)
-        DGC_FAIL(DGC_ERR_INVALID, "%s: dtype must be DGC_BF16 or DGC_F16 (got %d)", who, (int)dtype);
+    if (!is16(dtype)) DGC_FAIL(DGC_ERR_INVALID, "%s: dtype must be DGC_BF16 or DGC_F16 (got %d)", who, (int)dtype);
     if (!grad || !mmt || !vec || !vec32 || !p)
         DGC_FAIL(DGC_ERR_INVALID, "%s: null grad/mmt/vec/vec32/params", who);
-    DGC_TRY(k1_clip_check(clip_kind, ca.tab, who));
+    DGC_TRY(check_clip(who, clip_kind, ca.tab));
     if (p->update_memory != 0)
         DGC_FAIL(DGC_ERR_INVALID, "%s: update_memory must be 0 (the 16-bit state is masked from "
                                   "the payload, dgc_mask_packed16)", who);
@@ -708,10 +672,9 @@ int compress_begin16(const void* grad, void* mmt, void* vec, float* vec32, float
     const dim3 gd((unsigned)L.grid[BT_K1]);
     const uint16_t* g16 = static_cast<const uint16_t*>(grad);
     uint16_t *m16 = static_cast<uint16_t*>(mmt), *v16 = static_cast<uint16_t*>(vec);
-    if (dtype == DGC_BF16)
-        launch_k1_16<DGC_BF16>(nesterov, clip_kind, gd, s, g16, m16, v16, vec32, momentum, w, ot.start, (int)wt, ot, ca);
-    else
-        launch_k1_16<DGC_F16>(nesterov, clip_kind, gd, s, g16, m16, v16, vec32, momentum, w, ot.start, (int)wt, ot, ca);
+    with_h16(dtype, [&](auto DT) { with_bool(nesterov, [&](auto NEST) { with_clip(clip_kind, [&](auto CLIP) {
+        hipLaunchKernelGGL((k_compensate_list16<DT(), NEST(), CLIP()>), gd, dim3(kBlock), 0, s, g16, m16, v16, vec32, momentum,
+                           w, ot.start, (int)wt, ot, ca); }); }); });
     DGC_LAUNCHED();
     return DGC_OK;
 }
@@ -777,7 +740,7 @@ static int batch_layout(const dgc_batch_desc* b, HostTables& h) {
     }
     if (b->int32_indices && b->flat_numel > 2147483647LL)
         DGC_FAIL(DGC_ERR_OVERFLOW, "dgc_batch: int32 indices cannot address %lld elements", (long long)b->flat_numel);
-    if (b->dtype != DGC_F32 && b->dtype != DGC_BF16 && b->dtype != DGC_F16)
+    if (!float_dtype_ok(b->dtype))
         DGC_FAIL(DGC_ERR_DTYPE, "dgc_batch: dtype must be DGC_F32, DGC_BF16 or DGC_F16");
     h.build(in.data(), b->count, true);
     return DGC_OK;
@@ -788,7 +751,7 @@ static int batch_layout(const dgc_batch_desc* b, HostTables& h) {
 // dgc_mask_packed16), its wire values in the parameter dtype unless fp16_values, and its
 // threshold *= bound products rounded to the dtype.
 static SelCfg cfg_of_batch(const dgc_batch_desc* b) {
-    const bool half = b->dtype == DGC_BF16 || b->dtype == DGC_F16;
+    const bool half = is16(b->dtype);
     return SelCfg{(float)b->upper_bound, (float)b->lower_bound, b->max_iters, b->resample, b->momentum_masking,
                   b->fp16_values ? DGC_F16 : (half ? b->dtype : DGC_F32), b->int32_indices ? DGC_I32 : DGC_I64,
                   half ? 0 : (b->deferred_masking ? 2 : 1), half ? b->dtype : DGC_F32,
@@ -882,7 +845,7 @@ int batch_compress_begin(const dgc_batch_desc* b, const float* grad, const float
                          int32_t clip_kind = DGC_CLIP_NONE, ClipArg ca = ClipArg{nullptr, 0.f}) {
     HostTables h;
     SelWS w;
-    DGC_TRY(k1_clip_check(clip_kind, ca.tab, "dgc_batch_compress"));
+    DGC_TRY(check_clip("dgc_batch_compress", clip_kind, ca.tab));
     DGC_TRY(batch_ws(b, ws, ws_bytes, "dgc_batch_compress", h, w));
     const Layout& L = h.L;
     if ((!grad && !grads) || !mmt || !vec || !starts) DGC_FAIL(DGC_ERR_INVALID, "dgc_batch_compress: null pointer");

@@ -25,7 +25,8 @@
 // zero-element device tensor has a null data pointer): it gets no block, so none of its
 // pointers is read, and the step is the no-op the reference's is. With n > 0 a null
 // params[i] / grads[i] (or bufs[i], when a momentum buffer is in use) is refused.
-#include "dgc_common.hpp"
+#include "dispatch.hpp"
+#include "payload.hpp"
 
 namespace dgc {
 
@@ -196,7 +197,7 @@ extern "C" int dgc_sgd_step16(void* const* params, const void* const* grads, voi
     using namespace dgc;
     if (count < 0 || (count > 0 && (!params || !grads || !numels)))
         DGC_FAIL(DGC_ERR_INVALID, "dgc_sgd_step16: null tensor table");
-    if (dtype != DGC_BF16 && dtype != DGC_F16) DGC_FAIL(DGC_ERR_DTYPE, "dgc_sgd_step16: dtype must be bf16 or fp16");
+    if (!is16(dtype)) DGC_FAIL(DGC_ERR_DTYPE, "dgc_sgd_step16: dtype must be bf16 or fp16");
     const bool wd = weight_decay != 0.f, mom = wd && momentum != 0.f;
     if (count > 0 && mom && (!bufs || !first)) DGC_FAIL(DGC_ERR_INVALID, "dgc_sgd_step16: momentum needs buffers");
     DGC_TRY(sgd_check_table("dgc_sgd_step16", params, grads, bufs, numels, count, mom, kSgd16PerBlock));
@@ -219,16 +220,9 @@ extern "C" int dgc_sgd_step16(void* const* params, const void* const* grads, voi
         t.block0[t.count] = (int32_t)blocks;
         if (blocks == 0) continue;
         const dim3 gd((unsigned)blocks), bd(kBlock);
-#define DGC_SGD16(D) \
-        if (!wd) hipLaunchKernelGGL((k_sgd16<D, false, false>), gd, bd, 0, s, t, h); \
-        else if (!mom) hipLaunchKernelGGL((k_sgd16<D, true, false>), gd, bd, 0, s, t, h); \
-        else hipLaunchKernelGGL((k_sgd16<D, true, true>), gd, bd, 0, s, t, h);
-        if (dtype == DGC_BF16) {
-            DGC_SGD16(DGC_BF16)
-        } else {
-            DGC_SGD16(DGC_F16)
-        }
-#undef DGC_SGD16
+        // momentum only with weight decay (mom implies wd): three kernels per dtype, not four
+        with_h16(dtype, [&](auto DT) { with_bool(wd, [&](auto WD) { with_bool(mom, [&](auto MOM) {
+            hipLaunchKernelGGL((k_sgd16<DT(), WD(), WD() && MOM()>), gd, bd, 0, s, t, h); }); }); });
         DGC_LAUNCHED();
     }
     return DGC_OK;
@@ -263,12 +257,8 @@ extern "C" int dgc_sgd_step(float* const* params, const float* const* grads, flo
         }
         t.block0[t.count] = (int32_t)blocks;
         if (blocks == 0) continue;
-        if (!wd)
-            hipLaunchKernelGGL((k_sgd<false, false>), dim3((unsigned)blocks), dim3(kBlock), 0, s, t, h);
-        else if (!mom)
-            hipLaunchKernelGGL((k_sgd<true, false>), dim3((unsigned)blocks), dim3(kBlock), 0, s, t, h);
-        else
-            hipLaunchKernelGGL((k_sgd<true, true>), dim3((unsigned)blocks), dim3(kBlock), 0, s, t, h);
+        with_bool(wd, [&](auto WD) { with_bool(mom, [&](auto MOM) {   // mom implies wd: three kernels
+            hipLaunchKernelGGL((k_sgd<WD(), WD() && MOM()>), dim3((unsigned)blocks), dim3(kBlock), 0, s, t, h); }); });
         DGC_LAUNCHED();
     }
     return DGC_OK;
@@ -302,8 +292,6 @@ extern "C" int dgc_sgd_step(float* const* params, const float* const* grads, flo
 // [0, n) is skipped before any access. The scatter flagged both.
 namespace dgc {
 
-int64_t payload_layout(int64_t capacity, int vd, int id, int64_t* voff, int64_t* ioff);   // decompress.hip
-
 enum { kApply = 0, kApplyStash = 1, kApplyFixup = 2 };
 
 struct ApplySrc {
@@ -326,11 +314,9 @@ k_apply_entries(ApplySrc src, float* __restrict__ acc, float* __restrict__ p, co
                 float* __restrict__ stash, int64_t n, SgdHyper h) {
     const int r = (int)blockIdx.y;
     const char* base = src.payload + (int64_t)r * src.stride;
-    long long cnt = *reinterpret_cast<const long long*>(base);
-    cnt = cnt < 0 ? 0 : (cnt > src.capacity ? src.capacity : cnt);
+    const long long cnt = payload_count(base, src.capacity);
     for (long long e = (long long)blockIdx.x * kBlock + threadIdx.x; e < cnt; e += (long long)gridDim.x * kBlock) {
-        const long long i = ID == DGC_I32 ? (long long)reinterpret_cast<const int32_t*>(base + src.ioff)[e]
-                                          : (long long)reinterpret_cast<const int64_t*>(base + src.ioff)[e];
+        const long long i = load_wire_idx<ID>(base + src.ioff, e);
         if (i < 0 || i >= n) continue;
         const int64_t q = (int64_t)r * src.capacity + e;
         if (MODE == kApplyStash) {
@@ -416,21 +402,18 @@ static int apply_packed(const ApplySrc& src, int32_t world, float* acc, float* p
         DGC_LAUNCHED();
     }
     const dim3 dense((unsigned)ceil_div(n, (int64_t)kSgdPerBlock));
-    if (mom)
-        hipLaunchKernelGGL(k_sgd_zero_grad<true>, dense, block, 0, s, p, buf, n, first, h);
-    else
-        hipLaunchKernelGGL(k_sgd_zero_grad<false>, dense, block, 0, s, p, nullptr, n, 0, h);
-    DGC_LAUNCHED();
-    if (entries) {
-        if (mom)
-            hipLaunchKernelGGL((k_apply_entries<ID, kApplyFixup, true>), grid, block, 0, s, src, acc, p, buf, stash, n,
-                               h);
-        else
-            hipLaunchKernelGGL((k_apply_entries<ID, kApplyFixup, false>), grid, block, 0, s, src, acc, p, nullptr, stash,
-                               n, h);
-        DGC_LAUNCHED();
+    if (!mom) {   // the kernels without momentum take no buffer
+        buf = nullptr;
+        first = 0;
     }
-    return DGC_OK;
+    return with_bool(mom, [&](auto MOM) -> int {
+        hipLaunchKernelGGL(k_sgd_zero_grad<MOM()>, dense, block, 0, s, p, buf, n, first, h);
+        DGC_LAUNCHED();
+        if (entries) {
+            hipLaunchKernelGGL((k_apply_entries<ID, kApplyFixup, MOM()>), grid, block, 0, s, src, acc, p, buf, stash, n, h);
+            DGC_LAUNCHED();
+        }
+        return DGC_OK; });
 }
 
 }  // namespace dgc
@@ -446,15 +429,12 @@ extern "C" int dgc_apply_packed(const void* payload, int32_t world, int64_t rank
     using namespace dgc;
     if (!payload || !acc || !param) DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed: null payload, acc or param");
     if (world < 1 || world > 64) DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed: world %d outside 1..64", world);
-    if ((vdtype != DGC_F32 && vdtype != DGC_F16) || (idtype != DGC_I64 && idtype != DGC_I32))
-        DGC_FAIL(DGC_ERR_DTYPE, "dgc_apply_packed: unsupported value/index dtype (%d, %d)", vdtype, idtype);
+    DGC_TRY(check_wire("dgc_apply_packed", vdtype, idtype));
     if (capacity < 0 || n < 1) DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed: capacity < 0 or n < 1");
     if (ceil_div(n, (int64_t)kSgdPerBlock) > 0x7FFFFFFFLL) DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed: n too large");
     int64_t ioff = 0;
     const int64_t min_stride = payload_layout(capacity, vdtype, idtype, nullptr, &ioff);
-    if (rank_stride < min_stride)
-        DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed: rank_stride %lld < layout %lld", (long long)rank_stride,
-                 (long long)min_stride);
+    DGC_TRY(check_stride("dgc_apply_packed", rank_stride, min_stride));
     // lr >= 0 (a NaN fails too): the skip of a +0.0 slot needs -lr to carry the sign bit
     if (!(lr >= 0.f)) DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed: lr must be >= 0");
     const bool wd = weight_decay != 0.f, mom = wd && momentum != 0.f;
@@ -466,8 +446,7 @@ extern "C" int dgc_apply_packed(const void* payload, int32_t world, int64_t rank
     const ApplySrc src{static_cast<const char*>(payload), rank_stride, ioff, capacity};
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* stash = static_cast<float*>(ws);
-    if (idtype == DGC_I32) return apply_packed<DGC_I32>(src, world, acc, param, buf, first, n, h, mom, stash, s);
-    return apply_packed<DGC_I64>(src, world, acc, param, buf, first, n, h, mom, stash, s);
+    return with_id(idtype, [&](auto ID) { return apply_packed<ID()>(src, world, acc, param, buf, first, n, h, mom, stash, s); });
 }
 
 // ---------------------------------------------------------------- sparse step, multi-tensor
@@ -522,11 +501,9 @@ k_apply_entries_multi(ApplySrc src, float* __restrict__ acc, const dgc_apply_row
                       float* __restrict__ stash, int64_t n, ApplyGroups groups) {
     const int r = (int)blockIdx.y;
     const char* base = src.payload + (int64_t)r * src.stride;
-    long long cnt = *reinterpret_cast<const long long*>(base);
-    cnt = cnt < 0 ? 0 : (cnt > src.capacity ? src.capacity : cnt);
+    const long long cnt = payload_count(base, src.capacity);
     for (long long e = (long long)blockIdx.x * kBlock + threadIdx.x; e < cnt; e += (long long)gridDim.x * kBlock) {
-        const long long i = ID == DGC_I32 ? (long long)reinterpret_cast<const int32_t*>(base + src.ioff)[e]
-                                          : (long long)reinterpret_cast<const int64_t*>(base + src.ioff)[e];
+        const long long i = load_wire_idx<ID>(base + src.ioff, e);
         if (i < 0 || i >= n) continue;
         const int t = apply_row_of(rows, count, i, groups.count);
         const int64_t q = (int64_t)r * src.capacity + e;
@@ -612,8 +589,7 @@ extern "C" int dgc_apply_packed_multi(const void* payload, int32_t world, int64_
     if (!payload || !acc || !table || !hypers)
         DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed_multi: null payload, acc, table or hypers");
     if (world < 1 || world > 64) DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed_multi: world %d outside 1..64", world);
-    if ((vdtype != DGC_F32 && vdtype != DGC_F16) || (idtype != DGC_I64 && idtype != DGC_I32))
-        DGC_FAIL(DGC_ERR_DTYPE, "dgc_apply_packed_multi: unsupported value/index dtype (%d, %d)", vdtype, idtype);
+    DGC_TRY(check_wire("dgc_apply_packed_multi", vdtype, idtype));
     if (capacity < 0 || count < 1 || flat_numel < 1)
         DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed_multi: capacity < 0, count < 1 or flat_numel < 1");
     if (groups < 1 || groups > kApplyMaxGroups)
@@ -622,9 +598,7 @@ extern "C" int dgc_apply_packed_multi(const void* payload, int32_t world, int64_
         DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed_multi: dense_blocks outside [0, 2^31)");
     int64_t ioff = 0;
     const int64_t min_stride = payload_layout(capacity, vdtype, idtype, nullptr, &ioff);
-    if (rank_stride < min_stride)
-        DGC_FAIL(DGC_ERR_INVALID, "dgc_apply_packed_multi: rank_stride %lld < layout %lld", (long long)rank_stride,
-                 (long long)min_stride);
+    DGC_TRY(check_stride("dgc_apply_packed_multi", rank_stride, min_stride));
     ApplyGroups gs{};
     gs.count = groups;
     bool any_wd = false;
@@ -642,7 +616,6 @@ extern "C" int dgc_apply_packed_multi(const void* payload, int32_t world, int64_
     const ApplySrc src{static_cast<const char*>(payload), rank_stride, ioff, capacity};
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* stash = static_cast<float*>(ws);
-    if (idtype == DGC_I32)
-        return apply_packed_multi<DGC_I32>(src, world, acc, flat_numel, table, count, dense_blocks, gs, any_wd, stash, s);
-    return apply_packed_multi<DGC_I64>(src, world, acc, flat_numel, table, count, dense_blocks, gs, any_wd, stash, s);
+    return with_id(idtype, [&](auto ID) {
+        return apply_packed_multi<ID()>(src, world, acc, flat_numel, table, count, dense_blocks, gs, any_wd, stash, s); });
 }

@@ -61,20 +61,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "adam-compression_amd", "csrc")
 
 
-def makefile_flags():
+def makefile_vars(csrc=CSRC):
+    """The variables of csrc/Makefile as written (continuation lines joined)."""
+    text = open(os.path.join(csrc, "Makefile")).read().replace("\\\n", " ")
+    return dict(re.findall(r"^(\w+)\s*[:?]?=\s*(.*)$", text, re.M))
+
+
+def makefile_flags(csrc=CSRC):
     """CXXFLAGS of csrc/Makefile with its variables filled in (ARCH default, no EXTRA)."""
-    text = open(os.path.join(CSRC, "Makefile")).read().replace("\\\n", " ")
-    var = dict(re.findall(r"^(\w+)\s*[:?]?=\s*(.*)$", text, re.M))
+    var = makefile_vars(csrc)
     flags = var["CXXFLAGS"].replace("$(ARCH)", var["ARCH"].strip()).replace("$(EXTRA)", "")
     return var["HIPCC"].strip(), flags.split()
 
 
-def compile_asm(src):
-    hipcc, flags = makefile_flags()
+def compile_asm(src, csrc=CSRC):
+    hipcc, flags = makefile_flags(csrc)
     out = tempfile.NamedTemporaryFile(suffix=".s", delete=False)
     out.close()
     cmd = [hipcc] + flags + ["-Wno-unused-command-line-argument", "--cuda-device-only", "-S", src, "-o", out.name]
-    subprocess.run(cmd, cwd=CSRC, check=True)
+    subprocess.run(cmd, cwd=csrc, check=True)
     text = open(out.name).read()
     os.unlink(out.name)
     return text
