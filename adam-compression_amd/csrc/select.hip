@@ -59,6 +59,7 @@
 #include "select_tiles.hpp"        // tile loads, list append, task(), deferred masking
 #include "select_k1.hpp"           // K1 with lists
 #include "select_k1_16.hpp"        // K1 with lists over 16-bit state (the flat bucket)
+#include "select_k1_g16.hpp"       // K1 with lists over fp32 state and a 16-bit gradient (the flat bucket)
 #include "select_state.hpp"        // sel_init_tensor, decide_tensor
 #include "select_thresholds.hpp"   // K3
 #include "select_count.hpp"        // list count, select pass, lowering
@@ -572,6 +573,16 @@ constexpr unsigned kK1FlatLds = 48u << 10;
 // tensor can take them.
 static bool k1_stride_ok(bool sampled, int64_t stride) { return !sampled || (stride >= 4 && stride < (1LL << 30)); }
 
+// The samples that fall into an unpadded tensor's scalar tail [done, n), read back from vec
+// once the tail is compensated: start + q * stride >= done. cnt: the tensor's sample count.
+static int sample_tail(const float* vec, int64_t done, int64_t s_start, int64_t s_stride, int64_t cnt, float* samples,
+                       hipStream_t s) {
+    const int64_t q_first = done >= s_start ? ceil_div(done - s_start, s_stride) : 0;
+    const int64_t c = cnt - q_first;
+    if (c <= 0) return DGC_OK;
+    return sample_strided_launch(vec, s_start + q_first * s_stride, s_stride, c, samples + q_first, s);
+}
+
 // K1 of one tensor (ONE: the flat bucket) or of a batch; the two callers differ in the tables they pass.
 template <bool ONE, typename... Args>
 static void launch_k1(bool nesterov, int32_t clip_kind, unsigned lds, dim3 gd, hipStream_t s, Args... args) {
@@ -620,13 +631,48 @@ int compress_begin(const float* grad, float* mmt, float* vec, float momentum, bo
         const int64_t done = (n / 4) * 4;
         DGC_TRY(compensate_clip(grad + done, mmt + done, vec + done, nullptr, n - done, momentum, nesterov, true,
                                 nullptr, 0, 1, 0, clip_kind, ca, s));
-        if (sampled) {
-            // samples in the tail: start + q*stride >= done
-            const int64_t q_first = done >= s_start ? ceil_div(done - s_start, s_stride) : 0;
-            const int64_t c = cnt - q_first;
-            if (c > 0)
-                DGC_TRY(sample_strided_launch(vec, s_start + q_first * s_stride, s_stride, c, w.samples + q_first, s));
-        }
+        if (sampled) DGC_TRY(sample_tail(vec, done, s_start, s_stride, cnt, w.samples, s));
+    }
+    return DGC_OK;
+}
+
+// K1 of the flat bucket with fp32 momentum / velocity and a bf16 / fp16 gradient, widened in
+// K1's load (select_k1_g16.hpp): compress_begin on the widened gradient without the widened
+// copy, so dgc_compress_finish and dgc_compress_flush follow as they follow compress_begin.
+// Unclipped, and with no unfused fallback: what the listing kernel cannot take is refused.
+int compress_begin_g16(const void* grad, int32_t grad_dtype, float* mmt, float* vec, float momentum, bool nesterov,
+                       int64_t s_start, int64_t s_stride, const dgc_select_params* p, float* spec, void* ws,
+                       size_t ws_bytes, hipStream_t s) {
+    const char* who = "dgc_compress_begin_g16";
+    if (!is16(grad_dtype))
+        DGC_FAIL(DGC_ERR_DTYPE, "%s: grad_dtype must be DGC_BF16 or DGC_F16 (got %d)", who, (int)grad_dtype);
+    if (!grad || !mmt || !vec || !p) DGC_FAIL(DGC_ERR_INVALID, "%s: null grad/mmt/vec/params", who);
+    if (reinterpret_cast<uintptr_t>(grad) & 7u) DGC_FAIL(DGC_ERR_INVALID, "%s: grad must be 8-B aligned", who);
+    if (!aligned16(mmt) || !aligned16(vec)) DGC_FAIL(DGC_ERR_INVALID, "%s: mmt and vec must be 16-B aligned", who);
+    const int64_t n = p->numel;
+    const bool sampled = n != p->num_samples;
+    if (!k1_stride_ok(sampled, s_stride))
+        DGC_FAIL(DGC_ERR_INVALID, "%s: sample stride %lld outside [4, 2^30)", who, (long long)s_stride);
+    DGC_TRY(compress_check(p, nullptr, nullptr, s_start, s_stride, 1, false));
+    Layout L;
+    SelWS w;
+    OneTable ot{};
+    DGC_TRY(one_ws(p, s_start, s_stride, 1, spec, ws, ws_bytes, L, w, ot));
+    if (L.grid[BT_K1] < 1 || L.grid[BT_K1] > 0x7FFFFFFFLL) DGC_FAIL(DGC_ERR_INVALID, "%s: n too large", who);
+    // the fp32 flat launch's occupancy policy (kK1FlatLds): 10 of its 12 KB in flight per wave
+    const bool wt = write_through(n);
+    const uint16_t* g16 = static_cast<const uint16_t*>(grad);
+    with_h16(grad_dtype, [&](auto GD) { with_bool(nesterov, [&](auto NEST) {
+        hipLaunchKernelGGL((k_compensate_list_g16<GD(), NEST()>), dim3((unsigned)L.grid[BT_K1]), dim3(kBlock),
+                           wt ? 0u : kK1FlatLds, s, g16, mmt, vec, momentum, w, ot.start, (int)wt, ot); }); });
+    DGC_LAUNCHED();
+    if (n & 3) {   // scalar tail (< 4 elements) incl. its samples; its segment is marked spilled
+        const int64_t done = (n / 4) * 4;
+        with_h16(grad_dtype, [&](auto GD) { with_bool(nesterov, [&](auto NEST) {
+            hipLaunchKernelGGL((k_compensate_tail_g16<GD(), NEST()>), dim3(1), dim3(64), 0, s, g16, mmt, vec, done, n,
+                               momentum); }); });
+        DGC_LAUNCHED();
+        if (sampled) DGC_TRY(sample_tail(vec, done, s_start, s_stride, ceil_div(n - s_start, s_stride), w.samples, s));
     }
     return DGC_OK;
 }
@@ -998,6 +1044,15 @@ extern "C" int dgc_compress_begin16_clip(const void* grad, void* mmt, void* vec,
                                  const_cast<float*>(spec_threshold), ws, ws_bytes, dtype,
                                  static_cast<hipStream_t>(stream), clip_kind, dgc::ClipArg{clip, clip_value},
                                  "dgc_compress_begin16_clip");
+}
+
+extern "C" int dgc_compress_begin_g16(const void* grad, int32_t grad_dtype, float* mmt, float* vec, float momentum,
+                                      int32_t nesterov, int64_t sample_start, int64_t sample_stride,
+                                      const dgc_select_params* params, const float* spec_threshold, void* ws,
+                                      size_t ws_bytes, void* stream) {
+    return dgc::compress_begin_g16(grad, grad_dtype, mmt, vec, momentum, nesterov != 0, sample_start, sample_stride,
+                                   params, const_cast<float*>(spec_threshold), ws, ws_bytes,
+                                   static_cast<hipStream_t>(stream));
 }
 
 extern "C" int dgc_compress_finish(float* vec, float* mmt, int64_t sample_start, int64_t sample_stride,

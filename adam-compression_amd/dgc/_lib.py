@@ -336,6 +336,8 @@ _SIGNATURES = {
                                                    _I64, _F, _I32, _I32, _I32, _P, _F, _P]),
     "dgc_compress_begin16_clip": (ctypes.c_int, [_P, _P, _P, _P, _F, _I32, _I64, _I64, ctypes.POINTER(SelectParams),
                                                  _P, _I32, _P, _F, _P, _SZ, _I32, _P]),
+    "dgc_compress_begin_g16": (ctypes.c_int, [_P, _I32, _P, _P, _F, _I32, _I64, _I64, ctypes.POINTER(SelectParams), _P,
+                                              _P, _SZ, _P]),
     "dgc_sgd_step": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(_P),
                                     ctypes.POINTER(_I64), ctypes.POINTER(_I32), _I32, _F, _F, _F, _F, _I32, _P]),
     "dgc_sgd_step16": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(_P),

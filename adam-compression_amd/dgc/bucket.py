@@ -33,6 +33,14 @@ pure on the image and the 16-bit state is masked from the payload
 (``dgc_mask_packed16``), so nothing is ever deferred. The receive side is the 16-bit
 packed decompress (``dgc_decompress_packed16``: dense fill, one exchange part).
 
+``grad_dtype=torch.bfloat16`` / ``torch.float16`` with fp32 ``dtype``: fp32 momentum and
+velocity under a 16-bit gradient, what the reference's compensate computes through torch's
+type promotion (dgc/memory.py:50-63: every op in fp32 on the exactly widened gradient), so
+bit for bit the fp32 step on ``grad.float()``. ``compensate`` takes the 16-bit gradient
+(``dgc_compress_begin_g16``: K1 loads four 16-bit elements per lane and widens them in
+registers, 18 B/elem, no widened copy); everything after it is the fp32 bucket's, ``out``
+and ``apply``'s parameters fp32. No ``clip`` (a 16-bit gradient is clipped in its own dtype).
+
 ``clip=``: the reference's local gradient clipping (a ``dgc.clip_grad.ClipSpec``, or one of
 ``clip_grad_norm_`` (norm 2 / inf) / ``clip_grad_value_``, bare or as a ``functools.partial``)
 fused into K1's load of the gradient: the bucket's statistic (``dgc_grad_stats`` /
@@ -66,16 +74,18 @@ __all__ = ["DGCBucket", "algorithmic_bytes"]
 SEG = 1024   # the kernels' segment: a 16-bit bucket pads its state to whole segments
 
 
-def algorithmic_bytes(numel, k, num_samples, world, vbytes=4, ibytes=8, sbytes=4):
+def algorithmic_bytes(numel, k, num_samples, world, vbytes=4, ibytes=8, sbytes=4, gbytes=None):
     """Bytes one rank must move per step:
     compensate 20N + select re-read 4N + dense decompress write 4N, the samples 4S,
     masking 8k, payload written k(vb+ib) + gathered W*k(vb+ib) read, scatter RMW 8Wk.
     sbytes: the state element size. 2 (a 16-bit bucket): compensate 3 x 2N read + 2 x 2N
     written + the 4N image, the image re-read 4N, the decompress write 2N, masking and
-    scatter 2 B per entry and array."""
+    scatter 2 B per entry and array. gbytes: the gradient's element size where it is not
+    the state's (2 with sbytes 4, ``grad_dtype``: compensate 18N)."""
     image = 4 if sbytes < 4 else 0
-    return ((6 * sbytes + image + 4) * numel + 4 * num_samples + 2 * sbytes * k + (1 + world) * k * (vbytes + ibytes)
-            + 2 * sbytes * world * k)
+    gbytes = sbytes if gbytes is None else gbytes
+    return ((5 * sbytes + gbytes + image + 4) * numel + 4 * num_samples + 2 * sbytes * k
+            + (1 + world) * k * (vbytes + ibytes) + 2 * sbytes * world * k)
 
 
 class DGCBucket(ReceiveSide):
@@ -83,13 +93,24 @@ class DGCBucket(ReceiveSide):
                  sample_ratio=0.01, compress_upper_bound=1.3, compress_lower_bound=0.8,
                  max_adaptation_iters=10, resample=True, fp16_values=False, int32_indices=False,
                  device=None, world_size=None, seed=42, fill="auto", deferred_masking=True, exchange_parts="auto",
-                 resample_order="topk", dtype=torch.float32, clip=None):
+                 resample_order="topk", dtype=torch.float32, clip=None, grad_dtype=None):
         if fill not in ("auto", "inline", "allgather", "sparse"):
             raise ValueError(f"fill must be 'auto', 'inline', 'allgather' or 'sparse', not {fill!r}")
         if dtype not in (torch.float32,) + _lib.HALF:
             raise NotImplementedError(f"DGCBucket: fp32, bf16 or fp16 parameters (got {dtype})")
+        if grad_dtype not in (None, torch.float32) + _lib.HALF:
+            raise NotImplementedError(f"DGCBucket: fp32, bf16 or fp16 gradients (got grad_dtype={grad_dtype})")
         self.dtype = dtype
         self.half = dtype in _lib.HALF
+        if grad_dtype not in (None, dtype):
+            if self.half:
+                raise ValueError(f"DGCBucket: {dtype} state takes {dtype} gradients (got grad_dtype={grad_dtype}); "
+                                 "a 16-bit gradient onto fp32 state is dtype=torch.float32 with grad_dtype")
+            if clip is not None:
+                raise NotImplementedError(f"DGCBucket: clip with grad_dtype={grad_dtype} onto fp32 state (a 16-bit "
+                                          "gradient is clipped in its own dtype before it is widened; not built)")
+        # mixed: fp32 state, a bf16 / fp16 gradient widened in K1's load (dgc_compress_begin_g16)
+        self.grad_dtype = grad_dtype if grad_dtype in _lib.HALF and not self.half else None
         if self.half and fill in ("allgather", "sparse"):
             raise NotImplementedError(f"DGCBucket: fill={fill!r} on {dtype} parameters (the 16-bit decompress is the "
                                       "dense fill with the scatter)")
@@ -105,6 +126,10 @@ class DGCBucket(ReceiveSide):
         self.numel = N = int(numel)
         self.k, self.num_samples, self.top_k_samples, self.stride = DGCCompressor._attributes(
             N, *DGCCompressor._normalized(compress_ratio, sample_ratio))
+        if self.grad_dtype is not None and N != self.num_samples and self.stride < 4:
+            raise NotImplementedError(f"DGCBucket: grad_dtype={grad_dtype} onto fp32 state needs a sample stride >= 4 "
+                                      f"(sample_ratio {sample_ratio} gives {self.stride}): the listing K1 has no "
+                                      "unfused fallback")
         self.momentum, self.nesterov = float(momentum), bool(nesterov)
         self.world = world_size or (dist.get_world_size() if dist.is_initialized() else 1)
         self.momentum_masking = bool(momentum_masking)
@@ -183,6 +208,13 @@ class DGCBucket(ReceiveSide):
         decompress met an index or a gathered count out of range (``status``)."""
         self.status.check()
         L = self._L
+        if self.grad_dtype is not None:
+            # exactly N elements of grad_dtype: K1 reads the gradient to its last element and widens it
+            dev = self._mmt.device
+            if not (torch.is_tensor(grad) and grad.is_cuda and grad.device == dev and grad.dtype == self.grad_dtype
+                    and grad.is_contiguous() and grad.numel() == self.numel and grad.data_ptr() % 16 == 0):
+                raise ValueError(f"DGCBucket.compensate: grad must be a contiguous, 16-B aligned {self.grad_dtype} "
+                                 f"CUDA tensor of {self.numel} elements on {dev}")
         self.rx.begin()
         self.start = self.rng.randint(0, self.stride - 1) if self.sampled else 0
         self.cnt = (self.numel - self.start + self.stride - 1) // self.stride if self.sampled else self.numel
@@ -192,6 +224,14 @@ class DGCBucket(ReceiveSide):
                     and grad.numel() == self.numel and grad.data_ptr() % 16 == 0):
                 raise ValueError(f"DGCBucket.compensate: grad must be a contiguous, 16-B aligned {self.dtype} CUDA "
                                  f"tensor of {self.numel} elements")
+        if self.grad_dtype is not None:   # (never with a clip)
+            _lib.check(L.dgc_compress_begin_g16(grad.data_ptr(), _lib.VD[self.grad_dtype], self._mmt.data_ptr(),
+                                                self._vec.data_ptr(), self.momentum, int(self.nesterov), self.start,
+                                                self.stride, ctypes.byref(self.params), self.spec.data_ptr(),
+                                                self.ws.data_ptr(), self.ws.numel(), _lib.stream_of(self.device)),
+                       "dgc_compress_begin_g16")
+            self._pending = False   # K1 applied it
+            return
         clip = None
         if self.clip is not None:   # the bucket's statistic and coefficient, then the clip in K1's load
             self.clip_coef = self.clip.table_coefs((ctypes.c_void_p * 1)(grad.data_ptr()), self._clip_numel, 1,

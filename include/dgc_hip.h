@@ -34,6 +34,9 @@
  *                         16-bit tensor: every op rounds to the dtype)
  *   dgc_compress_begin16  compensate on 16-bit state + strided sample  dgc/memory.py:50-63,
  *                         (+ the fp32 image and the candidate lists)   dgc/compression.py:113-121
+ *   dgc_compress_begin_g16  compensate on fp32 state from a bf16 / fp16 gradient (torch's type
+ *                         promotion widens it exactly)                 dgc/memory.py:50-63,
+ *                         + strided sample (+ the candidate lists)     dgc/compression.py:113-121
  *
  * Conventions
  *   - All tensor pointers are DEVICE pointers owned by the caller (PyTorch's caching
@@ -697,6 +700,29 @@ int dgc_decompress_packed16(const void* payload, int32_t world, int64_t rank_str
 int dgc_compress_begin16(const void* grad, void* mmt, void* vec, float* vec32, float momentum, int32_t nesterov,
                          int64_t sample_start, int64_t sample_stride, const dgc_select_params* params,
                          const float* spec_threshold, void* ws, size_t ws_bytes, int32_t dtype, void* stream);
+/* The mixed flat bucket: dgc_compress_begin for ONE tensor whose momentum and velocity are
+ * fp32 and whose gradient is 16-bit (grad_dtype = DGC_BF16 / DGC_F16). The reference's
+ * compensate (dgc/memory.py:50-63: mmt.add_(grad), mul_, vec.add_(mmt).add_(grad)) on fp32
+ * state and a 16-bit gradient runs every op in fp32 on the exactly widened gradient (torch's
+ * type promotion of an in-place op), and its strided sample (dgc/compression.py:113-121)
+ * reads the fp32 velocity: the step is bit for bit dgc_compress_begin on grad.float(). This
+ * entry point is that call with the widening in K1's load of the gradient (8 bytes per four
+ * elements, widened in registers): 18 B/elem instead of the 6 B/elem of the widened copy
+ * plus the 20 B/elem of dgc_compress_begin, and no 4 B/elem buffer. On return mmt, vec and
+ * everything a later call reads from the workspace are what dgc_compress_begin leaves on
+ * the widened gradient, so dgc_compress_finish, dgc_compress_flush and the receive side
+ * follow unchanged, with the same params, start, stride and ws (dgc_compress_workspace,
+ * zero-filled before its first call).
+ *   grad: exactly params->numel elements of grad_dtype, never read past them, 8-B aligned.
+ *   mmt, vec: params->numel floats, 16-B aligned. A sampled tensor's stride in [4, 2^30).
+ * Before anything is launched: DGC_ERR_DTYPE for any other grad_dtype; DGC_ERR_INVALID for
+ * a null pointer, a misaligned one, such a stride, or what dgc_compress_begin refuses. There
+ * is no unfused fallback and no clipped form (clipping a 16-bit gradient rounds to its dtype
+ * before the widening: dgc_compress_begin16_clip's clip16, not built here). */
+int dgc_compress_begin_g16(const void* grad, int32_t grad_dtype, float* mmt, float* vec, float momentum,
+                           int32_t nesterov, int64_t sample_start, int64_t sample_stride,
+                           const dgc_select_params* params, const float* spec_threshold, void* ws, size_t ws_bytes,
+                           void* stream);
 /* bad_flag of dgc_mask_indices16 / dgc_decompress16 / dgc_decompress_packed16: a device
  * or host-mapped int32 that receives 1 when an index is outside [-n, n) (negative ones
  * wrap as in index_put_ / index_fill_; the packed form takes none below 0) and 2 when a

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""What the compiler made of K1 (k_compensate_list), of K1-16 (k_compensate_list16) and of
-the plain compensate kernels.
+"""What the compiler made of K1 (k_compensate_list), of K1-16 (k_compensate_list16), of K1-mixed
+(k_compensate_list_g16: fp32 state, 16-bit gradient) and of the plain compensate kernels.
 
 Host only, no GPU: compiles a .hip file of adam-compression_amd/csrc to gfx950 assembly
 with the Makefile's flags (read from the Makefile) and prints, per kernel instantiation,
@@ -14,7 +14,7 @@ with the Makefile's flags (read from the Makefile) and prints, per kernel instan
                          compiler could not prove)
   walks                  the walks through the kernel that the figures below range over (+: cut off)
   stream                 non-temporal streaming loads on a walk, a wave's 12: 16-B ones in K1,
-                         8-B ones in K1-16
+                         8-B ones in K1-16, eight 16-B and four 8-B ones in K1-mixed
   before-vm-wait         how many of them are issued before the first wait on the vector
                          memory counter that waits for one of them
   waits-before / mem     waits in front of the first streaming load / those of them that
@@ -34,7 +34,7 @@ without a warning:
     what a plain 64-bit read compiles to (a pointer, an int64 table entry): one that carried
     `nt` would be counted, and two streaming loads of a lane that the compiler merged into one
     dwordx4 would not. The gradient's partial last group (ld_tail16) is 2-B loads without
-    `nt`, so counts as `mem`, never as a streaming load;
+    `nt`, so counts as `mem`, never as a streaming load. K1-mixed counts both widths;
   - a vmcnt wait that finds nothing outstanding on the walk is taken for the wait of a loop
     whose load stands below it in the text (task_first's search) and counted as
     memory-dependent; a redundant wait would be counted the same way;
@@ -44,7 +44,7 @@ without a warning:
   - loads and stores retire in issue order on their counter (true of gfx9 vector memory;
     scalar loads are only ever waited for with lgkmcnt(0) here).
 
-  tools/k1_isa.py                      # K1's twelve instantiations and K1-16's twelve, as a markdown table
+  tools/k1_isa.py                      # K1's twelve instantiations, K1-16's twelve and K1-mixed's four, as a markdown table
   tools/k1_isa.py --compensate         # k_compensate4 / k_compensate_mt (compensate.hip)
   tools/k1_isa.py --asm FILE.s         # read an assembly file instead of compiling
   tools/k1_isa.py --trace 'ILb1ELb1ELi0E'   # the memory operations and waits of one kernel
@@ -273,6 +273,9 @@ def pretty(name):
     m = re.search(r"k_compensate_list16ILi(\d)ELb(\d)ELi(\d)E", name)
     if m:
         return "K1-16 DT=%s NEST=%s CLIP=%s" % m.groups()
+    m = re.search(r"k_compensate_list_g16ILi(\d)ELb(\d)E", name)
+    if m:
+        return "K1-mixed GD=%s NEST=%s" % m.groups()
     m = re.search(r"\d+(k_compensate\w*?)I(\w+?)EEv", name)
     return "%s<%s>" % m.groups() if m else name
 
@@ -283,7 +286,7 @@ def main():
     ap.add_argument("--compensate", action="store_true", help="compensate.hip's k_compensate4 / k_compensate_mt")
     ap.add_argument("--trace", metavar="REGEX", help="print the memory operations and waits of the kernels matching it")
     a = ap.parse_args()
-    src, name_re = ("compensate.hip", r"k_compensate(4|_mt)I") if a.compensate else ("select.hip", r"k_compensate_list(16)?I")
+    src, name_re = ("compensate.hip", r"k_compensate(4|_mt)I") if a.compensate else ("select.hip", r"k_compensate_list(16|_g16)?I")
     text = open(a.asm).read() if a.asm else compile_asm(src)
     print("| kernel | vgpr | occ | launched | scratch | flat | walks | stream | before-vm-wait | waits-before / mem | mem-to-last |")
     print("|---|---|---|---|---|---|---|---|---|---|---|")
@@ -291,11 +294,12 @@ def main():
     cap = None if (a.asm or a.compensate) else flat_launch_waves()   # an --asm file's launch is not known
     for name, body, tr in kernels(text, name_re):
         occ = trailer(tr, "Occupancy")
-        one = re.search(r"k_compensate_listILb\dELb1E", name)
+        one = re.search(r"k_compensate_listILb\dELb1E|k_compensate_list_g16I", name)
         launched = "%d" % occ if not (cap and one) else "%d / %d" % (min(occ, cap), occ)
-        # K1-16 streams 8-B loads and has no LDS-bounded launch (`one` does not match it)
-        walks, cut = scan(body, nstream=None if a.compensate else kSegLoads,
-                          stream_op="dwordx2" if "k_compensate_list16I" in name else "dwordx4")
+        # K1-16 streams 8-B loads and has no LDS-bounded launch (`one` does not match it);
+        # K1-mixed streams both widths under K1's launch
+        width = "dwordx2" if "k_compensate_list16I" in name else "dwordx[24]" if "k_compensate_list_g16I" in name else "dwordx4"
+        walks, cut = scan(body, nstream=None if a.compensate else kSegLoads, stream_op=width)
         if a.trace:
             if re.search(a.trace, name) and walks:
                 for what, w in (("fewest", min(walks, key=lambda w: w.mem_to_last)), ("most", max(walks, key=lambda w: w.mem_to_last))):
