@@ -57,9 +57,8 @@
 #include "select_types.hpp"        // constants, list slots, TDesc / SelState / SetG / SelCfg / SelWS
 #include "select_layout.hpp"       // host layout, workspace carve, k_put_one / k_put_starts
 #include "select_tiles.hpp"        // tile loads, list append, task(), deferred masking
-#include "select_k1.hpp"           // K1 with lists
+#include "select_k1.hpp"           // K1 with lists over fp32 state (an fp32 or, the flat bucket, a 16-bit gradient)
 #include "select_k1_16.hpp"        // K1 with lists over 16-bit state (the flat bucket)
-#include "select_k1_g16.hpp"       // K1 with lists over fp32 state and a 16-bit gradient (the flat bucket)
 #include "select_state.hpp"        // sel_init_tensor, decide_tensor
 #include "select_thresholds.hpp"   // K3
 #include "select_count.hpp"        // list count, select pass, lowering
@@ -584,43 +583,45 @@ static int sample_tail(const float* vec, int64_t done, int64_t s_start, int64_t 
 }
 
 // K1 of one tensor (ONE: the flat bucket) or of a batch; the two callers differ in the tables they pass.
+// gdt: the gradient's dtype. A 16-bit one (DGC_BF16 / DGC_F16) is the flat bucket's alone, unclipped.
 template <bool ONE, typename... Args>
-static void launch_k1(bool nesterov, int32_t clip_kind, unsigned lds, dim3 gd, hipStream_t s, Args... args) {
-    with_bool(nesterov, [&](auto NEST) { with_clip(clip_kind, [&](auto CLIP) {
-        hipLaunchKernelGGL((k_compensate_list<NEST(), ONE, CLIP()>), gd, dim3(kBlock), lds, s, args...); }); });
+static void launch_k1(int32_t gdt, bool nesterov, int32_t clip_kind, unsigned lds, dim3 gd, hipStream_t s,
+                      const void* grad, Args... args) {
+    with_bool(nesterov, [&](auto NEST) {
+        if (gdt == DGC_F32) {
+            with_clip(clip_kind, [&](auto CLIP) {
+                hipLaunchKernelGGL((k_compensate_list<NEST(), ONE, CLIP()>), gd, dim3(kBlock), lds, s,
+                                   static_cast<const float*>(grad), args...); });
+        } else if constexpr (ONE) {
+            with_h16(gdt, [&](auto GD) {
+                hipLaunchKernelGGL((k_compensate_list<NEST(), true, DGC_CLIP_NONE, GD()>), gd, dim3(kBlock), lds, s,
+                                   static_cast<const uint16_t*>(grad), args...); });
+        }
+    });
 }
 
-int compress_begin(const float* grad, float* mmt, float* vec, float momentum, bool nesterov, int64_t s_start,
-                   int64_t s_stride, const dgc_select_params* p, float* spec, void* ws, size_t ws_bytes,
-                   hipStream_t s, int32_t clip_kind = DGC_CLIP_NONE, ClipArg ca = ClipArg{nullptr, 0.f}) {
-    DGC_TRY(compress_check(p, nullptr, nullptr, s_start, s_stride, 1, false));
-    DGC_TRY(check_clip("dgc_compress", clip_kind, ca.tab));
-    if (!grad || !mmt || !vec) DGC_FAIL(DGC_ERR_INVALID, "dgc_compress: null grad/mmt/vec");
+// The list path of a one-tensor call (the flat bucket), fp32 state under a gradient of dtype
+// gdt: the workspace, K1 with the tensor's tables and sample start in its arguments, and the
+// scalar tail of the unpadded tensor. A 16-bit gradient is unclipped and has no k_put_one
+// path: its caller (who) refuses what yields no K1 workgroup.
+static int one_k1(const char* who, const void* grad, int32_t gdt, float* mmt, float* vec, float momentum,
+                  bool nesterov, int64_t s_start, int64_t s_stride, const dgc_select_params* p, float* spec, void* ws,
+                  size_t ws_bytes, int32_t clip_kind, ClipArg ca, hipStream_t s) {
     Layout L;
     SelWS w;
     OneTable ot{};
     DGC_TRY(one_ws(p, s_start, s_stride, 1, spec, ws, ws_bytes, L, w, ot));
+    const bool f32 = gdt == DGC_F32;
     const int64_t n = p->numel;
     const bool sampled = n != p->num_samples;
-    const int64_t cnt = sampled ? ceil_div(n - s_start, s_stride) : 0;
-    const bool list_path = aligned16(grad) && aligned16(mmt) && aligned16(vec) && k1_stride_ok(sampled, s_stride);
-    if (!list_path) {
-        hipLaunchKernelGGL(k_put_one, dim3(1), dim3(64), 0, s, w, ot);
-        DGC_LAUNCHED();
-        DGC_TRY(mask_flush(vec, mmt, L, w, s));   // a deferring finish left its masking to K1
-        DGC_TRY(compensate_clip(grad, mmt, vec, nullptr, n, momentum, nesterov, true, sampled ? w.samples : nullptr,
-                                s_start, s_stride, cnt, clip_kind, ca, s));
-        hipLaunchKernelGGL(k_no_lists, dim3(1), dim3(64), 0, s, w);
-        DGC_LAUNCHED();
-        return DGC_OK;
-    }
-    if (L.grid[BT_K1] > 0x7FFFFFFFLL) DGC_FAIL(DGC_ERR_INVALID, "dgc_compress: n too large");
+    if (L.grid[BT_K1] > 0x7FFFFFFFLL || (!f32 && L.grid[BT_K1] < 1)) DGC_FAIL(DGC_ERR_INVALID, "%s: n too large", who);
     if (L.grid[BT_K1] > 0) {
         StartChunk one{};   // the start (and the tables, ot) in the arguments: no k_put_one
         one.count = 1;
         one.start[0] = ot.start;
+        // a 16-bit gradient keeps the fp32 launch's occupancy policy: 10 of its 12 KB in flight per wave
         const bool wt = write_through(n);
-        launch_k1<true>(nesterov, clip_kind, wt ? 0u : kK1FlatLds, dim3((unsigned)L.grid[BT_K1]), s, grad, mmt, vec,
+        launch_k1<true>(gdt, nesterov, clip_kind, wt ? 0u : kK1FlatLds, dim3((unsigned)L.grid[BT_K1]), s, grad, mmt, vec,
                         momentum, w, one, (int)wt, ot, ca);
         DGC_LAUNCHED();
     } else {
@@ -629,17 +630,51 @@ int compress_begin(const float* grad, float* mmt, float* vec, float momentum, bo
     }
     if (n & 3) {   // scalar tail (< 4 elements) incl. its samples; its segment is marked spilled
         const int64_t done = (n / 4) * 4;
-        DGC_TRY(compensate_clip(grad + done, mmt + done, vec + done, nullptr, n - done, momentum, nesterov, true,
-                                nullptr, 0, 1, 0, clip_kind, ca, s));
-        if (sampled) DGC_TRY(sample_tail(vec, done, s_start, s_stride, cnt, w.samples, s));
+        if (f32) {
+            DGC_TRY(compensate_clip(static_cast<const float*>(grad) + done, mmt + done, vec + done, nullptr, n - done,
+                                    momentum, nesterov, true, nullptr, 0, 1, 0, clip_kind, ca, s));
+        } else {
+            with_h16(gdt, [&](auto GD) { with_bool(nesterov, [&](auto NEST) {
+                hipLaunchKernelGGL((k_compensate_tail_g16<GD(), NEST()>), dim3(1), dim3(64), 0, s,
+                                   static_cast<const uint16_t*>(grad), mmt, vec, done, n, momentum); }); });
+            DGC_LAUNCHED();
+        }
+        if (sampled) DGC_TRY(sample_tail(vec, done, s_start, s_stride, ceil_div(n - s_start, s_stride), w.samples, s));
     }
     return DGC_OK;
 }
 
+int compress_begin(const float* grad, float* mmt, float* vec, float momentum, bool nesterov, int64_t s_start,
+                   int64_t s_stride, const dgc_select_params* p, float* spec, void* ws, size_t ws_bytes,
+                   hipStream_t s, int32_t clip_kind = DGC_CLIP_NONE, ClipArg ca = ClipArg{nullptr, 0.f}) {
+    DGC_TRY(compress_check(p, nullptr, nullptr, s_start, s_stride, 1, false));
+    DGC_TRY(check_clip("dgc_compress", clip_kind, ca.tab));
+    if (!grad || !mmt || !vec) DGC_FAIL(DGC_ERR_INVALID, "dgc_compress: null grad/mmt/vec");
+    const int64_t n = p->numel;
+    const bool sampled = n != p->num_samples;
+    if (aligned16(grad) && aligned16(mmt) && aligned16(vec) && k1_stride_ok(sampled, s_stride))
+        return one_k1("dgc_compress", grad, DGC_F32, mmt, vec, momentum, nesterov, s_start, s_stride, p, spec, ws,
+                      ws_bytes, clip_kind, ca, s);
+    // the unfused fallback: no lists
+    Layout L;
+    SelWS w;
+    OneTable ot{};
+    DGC_TRY(one_ws(p, s_start, s_stride, 1, spec, ws, ws_bytes, L, w, ot));
+    hipLaunchKernelGGL(k_put_one, dim3(1), dim3(64), 0, s, w, ot);
+    DGC_LAUNCHED();
+    DGC_TRY(mask_flush(vec, mmt, L, w, s));   // a deferring finish left its masking to K1
+    DGC_TRY(compensate_clip(grad, mmt, vec, nullptr, n, momentum, nesterov, true, sampled ? w.samples : nullptr, s_start,
+                            s_stride, sampled ? ceil_div(n - s_start, s_stride) : 0, clip_kind, ca, s));
+    hipLaunchKernelGGL(k_no_lists, dim3(1), dim3(64), 0, s, w);
+    DGC_LAUNCHED();
+    return DGC_OK;
+}
+
 // K1 of the flat bucket with fp32 momentum / velocity and a bf16 / fp16 gradient, widened in
-// K1's load (select_k1_g16.hpp): compress_begin on the widened gradient without the widened
-// copy, so dgc_compress_finish and dgc_compress_flush follow as they follow compress_begin.
-// Unclipped, and with no unfused fallback: what the listing kernel cannot take is refused.
+// K1's load (k_compensate_list's GD): compress_begin on the widened gradient without the
+// widened copy, so dgc_compress_finish and dgc_compress_flush follow as they follow
+// compress_begin. Unclipped, and with no unfused fallback: what the listing kernel cannot
+// take is refused here, the rest is compress_begin's list path (one_k1).
 int compress_begin_g16(const void* grad, int32_t grad_dtype, float* mmt, float* vec, float momentum, bool nesterov,
                        int64_t s_start, int64_t s_stride, const dgc_select_params* p, float* spec, void* ws,
                        size_t ws_bytes, hipStream_t s) {
@@ -649,32 +684,11 @@ int compress_begin_g16(const void* grad, int32_t grad_dtype, float* mmt, float* 
     if (!grad || !mmt || !vec || !p) DGC_FAIL(DGC_ERR_INVALID, "%s: null grad/mmt/vec/params", who);
     if (reinterpret_cast<uintptr_t>(grad) & 7u) DGC_FAIL(DGC_ERR_INVALID, "%s: grad must be 8-B aligned", who);
     if (!aligned16(mmt) || !aligned16(vec)) DGC_FAIL(DGC_ERR_INVALID, "%s: mmt and vec must be 16-B aligned", who);
-    const int64_t n = p->numel;
-    const bool sampled = n != p->num_samples;
-    if (!k1_stride_ok(sampled, s_stride))
+    if (!k1_stride_ok(p->numel != p->num_samples, s_stride))
         DGC_FAIL(DGC_ERR_INVALID, "%s: sample stride %lld outside [4, 2^30)", who, (long long)s_stride);
     DGC_TRY(compress_check(p, nullptr, nullptr, s_start, s_stride, 1, false));
-    Layout L;
-    SelWS w;
-    OneTable ot{};
-    DGC_TRY(one_ws(p, s_start, s_stride, 1, spec, ws, ws_bytes, L, w, ot));
-    if (L.grid[BT_K1] < 1 || L.grid[BT_K1] > 0x7FFFFFFFLL) DGC_FAIL(DGC_ERR_INVALID, "%s: n too large", who);
-    // the fp32 flat launch's occupancy policy (kK1FlatLds): 10 of its 12 KB in flight per wave
-    const bool wt = write_through(n);
-    const uint16_t* g16 = static_cast<const uint16_t*>(grad);
-    with_h16(grad_dtype, [&](auto GD) { with_bool(nesterov, [&](auto NEST) {
-        hipLaunchKernelGGL((k_compensate_list_g16<GD(), NEST()>), dim3((unsigned)L.grid[BT_K1]), dim3(kBlock),
-                           wt ? 0u : kK1FlatLds, s, g16, mmt, vec, momentum, w, ot.start, (int)wt, ot); }); });
-    DGC_LAUNCHED();
-    if (n & 3) {   // scalar tail (< 4 elements) incl. its samples; its segment is marked spilled
-        const int64_t done = (n / 4) * 4;
-        with_h16(grad_dtype, [&](auto GD) { with_bool(nesterov, [&](auto NEST) {
-            hipLaunchKernelGGL((k_compensate_tail_g16<GD(), NEST()>), dim3(1), dim3(64), 0, s, g16, mmt, vec, done, n,
-                               momentum); }); });
-        DGC_LAUNCHED();
-        if (sampled) DGC_TRY(sample_tail(vec, done, s_start, s_stride, ceil_div(n - s_start, s_stride), w.samples, s));
-    }
-    return DGC_OK;
+    return one_k1(who, grad, grad_dtype, mmt, vec, momentum, nesterov, s_start, s_stride, p, spec, ws, ws_bytes,
+                  DGC_CLIP_NONE, ClipArg{nullptr, 0.f}, s);
 }
 
 // K1-16 of the flat bucket: 16-bit momentum / velocity / gradient, the velocity's fp32
@@ -908,8 +922,8 @@ int batch_compress_begin(const dgc_batch_desc* b, const float* grad, const float
     if (L.T <= 64) arg = start_chunk(h, starts, grads, 0);
     else DGC_TRY(put_starts(h, starts, grads, w, s));
     if (L.grid[BT_K1] > 0x7FFFFFFFLL) DGC_FAIL(DGC_ERR_INVALID, "dgc_batch_compress: too many segments");
-    launch_k1<false>(b->nesterov != 0, clip_kind, 0u, dim3((unsigned)L.grid[BT_K1]), s, grad, mmt, vec, b->momentum, w, arg,
-                     (int)write_through(L.nseg * kSeg), OneTable{}, ca);
+    launch_k1<false>(DGC_F32, b->nesterov != 0, clip_kind, 0u, dim3((unsigned)L.grid[BT_K1]), s, grad, mmt, vec, b->momentum,
+                     w, arg, (int)write_through(L.nseg * kSeg), OneTable{}, ca);
     DGC_LAUNCHED();
     return DGC_OK;
 }

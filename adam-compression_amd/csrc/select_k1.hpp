@@ -1,11 +1,40 @@
 // Selection, K1: compensate + strided sample + the speculative candidate lists
-// (k_compensate_list), and k_no_lists for a call whose vec no K1 listed. Relies on
+// (k_compensate_list, over fp32 state and an fp32 or a 16-bit gradient; k_compensate_tail_g16,
+// the scalar tail of the latter), and k_no_lists for a call whose vec no K1 listed. Relies on
 // select_layout.hpp (OneTable, StartChunk) and select_tiles.hpp (loads, list_append,
 // the deferred masking).
 #pragma once
 #include "select_tiles.hpp"
 
 namespace dgc {
+// ---- The 8-B streaming access to four 16-bit elements per lane: K1's 16-bit gradient and
+// all of K1-16 (select_k1_16.hpp).
+typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+
+// (uint2 in registers, like ld_nt's float4: an array of ext vectors is merged into one
+// wide value, and every conditional load of a part then copies — and waits for — the whole)
+__device__ __forceinline__ uint2 ld_nt(DGC_GLB const u2v* p) {
+    const u2v x = __builtin_nontemporal_load(p);
+    return make_uint2(x[0], x[1]);
+}
+__device__ __forceinline__ void st_nt(DGC_GLB u2v* p, uint2 v) {
+    const u2v x = {v.x, v.y};
+    __builtin_nontemporal_store(x, p);
+}
+
+template <int DT>
+__device__ __forceinline__ void unpack4(uint2 q, float (&x)[4]) {
+    x[0] = h16_to_f32<DT>((uint16_t)(q.x & 0xFFFFu));
+    x[1] = h16_to_f32<DT>((uint16_t)(q.x >> 16));
+    x[2] = h16_to_f32<DT>((uint16_t)(q.y & 0xFFFFu));
+    x[3] = h16_to_f32<DT>((uint16_t)(q.y >> 16));
+}
+
+// K1's gradient by dtype GD: the element the kernel's pointer names, a lane's streaming
+// load of four of them, and that load in registers.
+template <int GD> struct K1Grad { typedef uint16_t elem; typedef u2v load; typedef uint2 reg; };
+template <> struct K1Grad<DGC_F32> { typedef float elem; typedef float4 load; typedef float4 reg; };
+
 // task() that also returns the tensor's first block, blk[t], from the words the search
 // has loaded: the largest entry <= b of the ascending table (blk[0] = 0). K1 would
 // otherwise read it back, one more round trip ahead of its streaming loads.
@@ -123,6 +152,20 @@ __device__ __forceinline__ void k1_segment_end(uint32_t c, uint32_t mk, bool put
 // launch before every K1 (and its wait) — and the sample start in sc.
 // CLIP: the gradient clipped as it is used (dgc_common.hpp clip1), tensor t's
 // coefficient from ca; DGC_CLIP_NONE compiles to the unclipped kernel.
+// GD: the gradient's dtype. DGC_BF16 / DGC_F16 is the flat bucket's 16-bit gradient onto fp32
+// state (dgc_compress_begin_g16), one-tensor and unclipped: the reference's compensate there
+// (dgc/memory.py:50-63) runs every op in fp32 on the exactly widened gradient (torch's type
+// promotion of the in-place ops), so the step is bit for bit the fp32 one on grad.float().
+// The gradient is then an 8-B load per lane (512 B per instruction) widened by unpack4, with
+// the fp32 kernel's lane-to-element mapping: 18 B/elem where grad.float() and the fp32 kernel
+// move 6 + 20, and 10 KB in flight per wave. It is exactly n elements and the state is unpadded
+// (d.nv4 = n / 4 full groups): a live lane loads group gi of all three arrays only while
+// gi < n / 4, so the last byte read is below element 4 * (n / 4) <= n of each. The n & 3
+// elements after it are k_compensate_tail_g16's; their samples are read back from vec and
+// their segment is marked spilled (d.tail), as dgc_compress_begin does.
+// One template, not a sibling kernel: the parameter renames the fp32 instantiations and leaves
+// their code as it was, instruction for instruction (tools/kernel_hashes.py --diff reports
+// all twelve as renamed), and the 16-bit ones keep the sibling's registers and occupancy.
 //
 // The order of a wave's memory reads is the kernel's schedule (DESIGN.md §5 "K1's
 // schedule", tools/k1_isa.py): every state word it will need (the speculation thresholds,
@@ -138,10 +181,12 @@ __device__ __forceinline__ void k1_segment_end(uint32_t c, uint32_t mk, bool put
 // the kernel then reads words 0 and 2 of SelState and ignores them.
 static_assert(offsetof(SelState, t0) == 0 && offsetof(SelState, t_list) == 2 * sizeof(float),
               "K1's stand-in for a null spec reads SelState words 0 and 2");
-template <bool NEST, bool ONE, int CLIP>
+template <bool NEST, bool ONE, int CLIP, int GD = DGC_F32>
 __global__ void __launch_bounds__(kBlock)
-k_compensate_list(const float* __restrict__ g_flat, float* __restrict__ mmt_flat, float* __restrict__ vec_flat,
-                  float mom, SelWS w, StartChunk sc, int wt, OneTable ot, ClipArg ca) {
+k_compensate_list(const typename K1Grad<GD>::elem* __restrict__ g_flat, float* __restrict__ mmt_flat,
+                  float* __restrict__ vec_flat, float mom, SelWS w, StartChunk sc, int wt, OneTable ot, ClipArg ca) {
+    // (the reference clips a 16-bit gradient in its own dtype, clip16, which this kernel does not)
+    static_assert(GD == DGC_F32 || (ONE && CLIP == DGC_CLIP_NONE), "a 16-bit gradient: one tensor, unclipped");
     int64_t b0 = 0;   // the tensor's first block
     const int t = ONE ? 0 : task_first(w.bt[BT_K1], w.T, blockIdx.x, b0);
     const TDesc d = ONE ? ot.d : w.td[t];   // by value: stores below cannot alias it
@@ -191,9 +236,12 @@ k_compensate_list(const float* __restrict__ g_flat, float* __restrict__ mmt_flat
     const int gleft = ptrs ? (int)min((n >> 2) - seg4, (int64_t)(kSeg / 4)) : left;
     DGC_GLB float4* mmt = glb(reinterpret_cast<float4*>(mmt_flat + d.off) + seg4);
     DGC_GLB float4* vec = glb(reinterpret_cast<float4*>(vec_flat + d.off) + seg4);
-    const float* gsrc = !ptrs ? g_flat + d.off : (arg_start ? sc.grad[ONE ? 0 : t] : gptr_ws);
-    DGC_GLB const float4* g = glb(reinterpret_cast<const float4*>(gsrc) + seg4);
-    float4 gv[kSegTiles], mv[kSegTiles], vv[kSegTiles];
+    const typename K1Grad<GD>::elem* gsrc;
+    if constexpr (GD == DGC_F32) gsrc = !ptrs ? g_flat + d.off : (arg_start ? sc.grad[ONE ? 0 : t] : gptr_ws);
+    else gsrc = g_flat + d.off;   // flat, exactly n elements: its full groups only (gleft = left)
+    DGC_GLB const typename K1Grad<GD>::load* g = glb(reinterpret_cast<const typename K1Grad<GD>::load*>(gsrc) + seg4);
+    typename K1Grad<GD>::reg gv[kSegTiles];
+    float4 mv[kSegTiles], vv[kSegTiles];
 #pragma unroll
     for (int u = 0; u < kSegTiles; ++u) {
         if (u * 64 + lane < left) {
@@ -206,10 +254,12 @@ k_compensate_list(const float* __restrict__ g_flat, float* __restrict__ mmt_flat
         if (u * 64 + lane < gleft) gv[u] = ld_nt(g + u * 64 + lane);
     // the one wave that owns the partial last float4 of a pointer-table gradient patches
     // it in (wave-uniform branch, one lane loads)
-    if (ptrs && gleft < left && gleft >= 0) {
+    if constexpr (GD == DGC_F32) {
+        if (ptrs && gleft < left && gleft >= 0) {
 #pragma unroll
-        for (int u = 0; u < kSegTiles; ++u)
-            if (u * 64 + lane == gleft) gv[u] = ld_tail4(glb(gsrc), n);
+            for (int u = 0; u < kSegTiles; ++u)
+                if (u * 64 + lane == gleft) gv[u] = ld_tail4(glb(gsrc), n);
+        }
     }
 
     if (!ONE) def_rank = *grp_off + (long long)*seg_off;
@@ -238,11 +288,22 @@ k_compensate_list(const float* __restrict__ g_flat, float* __restrict__ mmt_flat
         bool hit = false;   // this lane's sample (at most one per float4: stride >= 4) joins the window
         float hv = 0.f;
         if (ok) {
-            const float4 gq = clip4<CLIP>(gv[u], cf);
-            x[0] = comp1<NEST, true>(gq.x, mv[u].x, vv[u].x, mom);
-            x[1] = comp1<NEST, true>(gq.y, mv[u].y, vv[u].y, mom);
-            x[2] = comp1<NEST, true>(gq.z, mv[u].z, vv[u].z, mom);
-            x[3] = comp1<NEST, true>(gq.w, mv[u].w, vv[u].w, mom);
+            // (the four lines twice: fed from one float4 filled under the `if constexpr`, the
+            // fp32 kernels came out with two instructions per tile in another order)
+            if constexpr (GD == DGC_F32) {
+                const float4 gq = clip4<CLIP>(gv[u], cf);
+                x[0] = comp1<NEST, true>(gq.x, mv[u].x, vv[u].x, mom);
+                x[1] = comp1<NEST, true>(gq.y, mv[u].y, vv[u].y, mom);
+                x[2] = comp1<NEST, true>(gq.z, mv[u].z, vv[u].z, mom);
+                x[3] = comp1<NEST, true>(gq.w, mv[u].w, vv[u].w, mom);
+            } else {
+                float gx[4];
+                unpack4<GD>(gv[u], gx);   // exact: the reference's promotion of the 16-bit gradient
+                x[0] = comp1<NEST, true>(gx[0], mv[u].x, vv[u].x, mom);
+                x[1] = comp1<NEST, true>(gx[1], mv[u].y, vv[u].y, mom);
+                x[2] = comp1<NEST, true>(gx[2], mv[u].z, vv[u].z, mom);
+                x[3] = comp1<NEST, true>(gx[3], mv[u].w, vv[u].w, mom);
+            }
             st_stream(mmt + u * 64 + lane, mv[u], wt);
             st_stream(vec + u * 64 + lane, vv[u], wt);
             const int64_t e = 4 * (seg4 + u * 64 + lane);
@@ -255,6 +316,20 @@ k_compensate_list(const float* __restrict__ g_flat, float* __restrict__ mmt_flat
     }
     // (the segment with the scalar tail, compensated outside K1, is marked spilled)
     k1_segment_end(c, mk, lane == 0 && live, d.tail && ls == d.nseg - 1, w.seg_lcnt + seg, w.st[t].spill[epoch & 1]);
+}
+
+// The n & 3 elements [begin, n) after the last full group of a 16-bit gradient: comp1 on the
+// widened gradient, one thread each (k_compensate1's arithmetic, compensate.hip, with the
+// 16-bit read).
+template <int GD, bool NEST>
+__global__ void k_compensate_tail_g16(const uint16_t* __restrict__ g16, float* __restrict__ mmt, float* __restrict__ vec,
+                                      int64_t begin, int64_t n, float mom) {
+    const int64_t i = begin + threadIdx.x;
+    if (i >= n) return;
+    float mv = mmt[i], vv = vec[i];
+    comp1<NEST, true>(h16_to_f32<GD>(g16[i]), mv, vv, mom);
+    mmt[i] = mv;
+    vec[i] = vv;
 }
 
 __global__ void k_no_lists(SelWS w) {

@@ -44,27 +44,6 @@
 #include "select_k1.hpp"
 
 namespace dgc {
-typedef uint32_t u2v __attribute__((ext_vector_type(2)));
-
-// (uint2 in registers, like ld_nt's float4: an array of ext vectors is merged into one
-// wide value, and every conditional load of a part then copies — and waits for — the whole)
-__device__ __forceinline__ uint2 ld_nt(DGC_GLB const u2v* p) {
-    const u2v x = __builtin_nontemporal_load(p);
-    return make_uint2(x[0], x[1]);
-}
-__device__ __forceinline__ void st_nt(DGC_GLB u2v* p, uint2 v) {
-    const u2v x = {v.x, v.y};
-    __builtin_nontemporal_store(x, p);
-}
-
-template <int DT>
-__device__ __forceinline__ void unpack4(uint2 q, float (&x)[4]) {
-    x[0] = h16_to_f32<DT>((uint16_t)(q.x & 0xFFFFu));
-    x[1] = h16_to_f32<DT>((uint16_t)(q.x >> 16));
-    x[2] = h16_to_f32<DT>((uint16_t)(q.y & 0xFFFFu));
-    x[3] = h16_to_f32<DT>((uint16_t)(q.y >> 16));
-}
-
 // x holds values of the dtype (round16's results): the narrowing is exact
 template <int DT>
 __device__ __forceinline__ uint2 pack4(const float (&x)[4]) {

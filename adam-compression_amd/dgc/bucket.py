@@ -208,22 +208,18 @@ class DGCBucket(ReceiveSide):
         decompress met an index or a gathered count out of range (``status``)."""
         self.status.check()
         L = self._L
-        if self.grad_dtype is not None:
-            # exactly N elements of grad_dtype: K1 reads the gradient to its last element and widens it
-            dev = self._mmt.device
-            if not (torch.is_tensor(grad) and grad.is_cuda and grad.device == dev and grad.dtype == self.grad_dtype
+        want = self.grad_dtype if self.grad_dtype is not None else self.dtype if self.half else None
+        if want is not None:
+            # exactly N elements of a 16-bit dtype: K1 (grad_dtype, which also names the state's
+            # device) and K1-16 read the gradient to its last element. A refusal draws no sample start
+            dev = self._mmt.device if self.grad_dtype is not None else None
+            if not (torch.is_tensor(grad) and grad.is_cuda and dev in (None, grad.device) and grad.dtype == want
                     and grad.is_contiguous() and grad.numel() == self.numel and grad.data_ptr() % 16 == 0):
-                raise ValueError(f"DGCBucket.compensate: grad must be a contiguous, 16-B aligned {self.grad_dtype} "
-                                 f"CUDA tensor of {self.numel} elements on {dev}")
+                raise ValueError(f"DGCBucket.compensate: grad must be a contiguous, 16-B aligned {want} CUDA tensor "
+                                 f"of {self.numel} elements" + (f" on {dev}" if dev is not None else ""))
         self.rx.begin()
         self.start = self.rng.randint(0, self.stride - 1) if self.sampled else 0
         self.cnt = (self.numel - self.start + self.stride - 1) // self.stride if self.sampled else self.numel
-        if self.half:
-            # exactly N elements of the dtype: K1-16 reads the gradient to its last element
-            if not (torch.is_tensor(grad) and grad.is_cuda and grad.dtype == self.dtype and grad.is_contiguous()
-                    and grad.numel() == self.numel and grad.data_ptr() % 16 == 0):
-                raise ValueError(f"DGCBucket.compensate: grad must be a contiguous, 16-B aligned {self.dtype} CUDA "
-                                 f"tensor of {self.numel} elements")
         if self.grad_dtype is not None:   # (never with a clip)
             _lib.check(L.dgc_compress_begin_g16(grad.data_ptr(), _lib.VD[self.grad_dtype], self._mmt.data_ptr(),
                                                 self._vec.data_ptr(), self.momentum, int(self.nesterov), self.start,

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What the compiler made of K1 (k_compensate_list), of K1-16 (k_compensate_list16), of K1-mixed
-(k_compensate_list_g16: fp32 state, 16-bit gradient) and of the plain compensate kernels.
+(k_compensate_list with a 16-bit GD: fp32 state, 16-bit gradient) and of the plain compensate kernels.
 
 Host only, no GPU: compiles a .hip file of adam-compression_amd/csrc to gfx950 assembly
 with the Makefile's flags (read from the Makefile) and prints, per kernel instantiation,
@@ -266,16 +266,20 @@ def flat_launch_waves():
     return CU_LDS // (int(m.group(1)) << int(m.group(2))) if m else None
 
 
+# K1-mixed: k_compensate_list<NEST, true, DGC_CLIP_NONE, GD> with GD = DGC_BF16 (1) or DGC_F16 (2)
+MIXED = r"k_compensate_listILb(\d)ELb1ELi0ELi([12])E"
+
+
 def pretty(name):
+    m = re.search(MIXED, name)
+    if m:
+        return "K1-mixed GD=%s NEST=%s" % (m.group(2), m.group(1))
     m = re.search(r"k_compensate_listILb(\d)ELb(\d)ELi(\d)E", name)
     if m:
         return "K1 NEST=%s ONE=%s CLIP=%s" % m.groups()
     m = re.search(r"k_compensate_list16ILi(\d)ELb(\d)ELi(\d)E", name)
     if m:
         return "K1-16 DT=%s NEST=%s CLIP=%s" % m.groups()
-    m = re.search(r"k_compensate_list_g16ILi(\d)ELb(\d)E", name)
-    if m:
-        return "K1-mixed GD=%s NEST=%s" % m.groups()
     m = re.search(r"\d+(k_compensate\w*?)I(\w+?)EEv", name)
     return "%s<%s>" % m.groups() if m else name
 
@@ -286,7 +290,7 @@ def main():
     ap.add_argument("--compensate", action="store_true", help="compensate.hip's k_compensate4 / k_compensate_mt")
     ap.add_argument("--trace", metavar="REGEX", help="print the memory operations and waits of the kernels matching it")
     a = ap.parse_args()
-    src, name_re = ("compensate.hip", r"k_compensate(4|_mt)I") if a.compensate else ("select.hip", r"k_compensate_list(16|_g16)?I")
+    src, name_re = ("compensate.hip", r"k_compensate(4|_mt)I") if a.compensate else ("select.hip", r"k_compensate_list(16)?I")
     text = open(a.asm).read() if a.asm else compile_asm(src)
     print("| kernel | vgpr | occ | launched | scratch | flat | walks | stream | before-vm-wait | waits-before / mem | mem-to-last |")
     print("|---|---|---|---|---|---|---|---|---|---|---|")
@@ -294,11 +298,11 @@ def main():
     cap = None if (a.asm or a.compensate) else flat_launch_waves()   # an --asm file's launch is not known
     for name, body, tr in kernels(text, name_re):
         occ = trailer(tr, "Occupancy")
-        one = re.search(r"k_compensate_listILb\dELb1E|k_compensate_list_g16I", name)
+        one = re.search(r"k_compensate_listILb\dELb1E", name)
         launched = "%d" % occ if not (cap and one) else "%d / %d" % (min(occ, cap), occ)
         # K1-16 streams 8-B loads and has no LDS-bounded launch (`one` does not match it);
         # K1-mixed streams both widths under K1's launch
-        width = "dwordx2" if "k_compensate_list16I" in name else "dwordx[24]" if "k_compensate_list_g16I" in name else "dwordx4"
+        width = "dwordx2" if "k_compensate_list16I" in name else "dwordx[24]" if re.search(MIXED, name) else "dwordx4"
         walks, cut = scan(body, nstream=None if a.compensate else kSegLoads, stream_op=width)
         if a.trace:
             if re.search(a.trace, name) and walks:

@@ -7,14 +7,21 @@ sorted:
 
   file  mangled-name  sha256
 
-The hash covers the function's text, without comments and with local labels (`.L...`, which
-carry the function's emission-order number) renamed by order of first appearance, and the kernel's
-`.amdhsa_kernel ... .end_amdhsa_kernel` block (registers, LDS, scratch). Two listings are equal
-exactly when the same functions were emitted with the same instructions and the same resources.
+The hash covers the function's text, without comments, with local labels (`.L...`, which
+carry the function's emission-order number) renamed by order of first appearance and with the
+function's own symbol (its label, its `.amdhsa_kernel NAME` line) replaced by a placeholder, and
+the kernel's `.amdhsa_kernel ... .end_amdhsa_kernel` block (registers, LDS, scratch). Two listings
+are equal exactly when the same functions were emitted with the same instructions and the same
+resources; a function that only changed its name (a new template parameter, say) keeps its hash,
+and --diff pairs it with its old name: a removed and an added function of one file with equal
+hashes print as `renamed  FILE  OLD -> NEW` (several with one hash: paired in sorted order).
 
   tools/kernel_hashes.py > new.txt                 # this tree
   tools/kernel_hashes.py --root OLD > old.txt      # another checkout of the repository
-  tools/kernel_hashes.py --diff old.txt new.txt    # exit 1 on any added, removed or changed function
+  tools/kernel_hashes.py --diff old.txt new.txt    # exit 1 on any added, removed, changed or renamed function
+
+Both listings of a --diff are made by the same version of this tool: listings of an earlier
+version hashed the name too.
 """
 import argparse
 import hashlib
@@ -48,6 +55,7 @@ def functions(text):
         # comments go: the compiler's loop notes name blocks by the same emission-order number
         body = "\n".join(ln.split(";")[0].rstrip() for ln in lines[i:j] + desc.get(name, []))
         body = re.sub(r"\.L\w+", lambda m: local.setdefault(m.group(0), ".L%d" % len(local)), body)
+        body = body.replace(name, "SELF")   # (also inside `.text.NAME`, its section)
         out[name] = hashlib.sha256(body.encode()).hexdigest()
     return out
 
@@ -67,12 +75,20 @@ def read_listing(path):
 
 def diff(old, new):
     a, b = read_listing(old), read_listing(new)
-    out = ["removed  %s  %s" % k for k in sorted(a.keys() - b.keys())]
-    out += ["added    %s  %s" % k for k in sorted(b.keys() - a.keys())]
-    out += ["changed  %s  %s" % k for k in sorted(a.keys() & b.keys()) if a[k] != b[k]]
+    gone, came = sorted(a.keys() - b.keys()), sorted(b.keys() - a.keys())
+    renamed = []
+    for k in list(gone):
+        twin = next((c for c in came if c[0] == k[0] and b[c] == a[k]), None)
+        if twin:
+            renamed.append((k[0], k[1], twin[1]))
+            gone.remove(k)
+            came.remove(twin)
+    changed = [k for k in sorted(a.keys() & b.keys()) if a[k] != b[k]]
+    out = ["removed  %s  %s" % k for k in gone] + ["added    %s  %s" % k for k in came]
+    out += ["changed  %s  %s" % k for k in changed] + ["renamed  %s  %s -> %s" % r for r in renamed]
     print("\n".join(out), end="\n" if out else "")
-    print("%d functions, %d removed, %d added, %d changed" % (
-        len(a), len(a.keys() - b.keys()), len(b.keys() - a.keys()), len(out) - len(a.keys() ^ b.keys())), file=sys.stderr)
+    print("%d functions, %d removed, %d added, %d changed, %d renamed" % (
+        len(a), len(gone), len(came), len(changed), len(renamed)), file=sys.stderr)
     return 1 if out else 0
 
 
